@@ -7,7 +7,11 @@ RCCL all-reduce of gradient buckets, overlapped with the backward) + Keras-Adam 
 synthetic batch resident in HBM.  Launch: ``python bench.py`` (N=1) or
 ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N``.
 
-Prints ONE JSON line (rank 0) with the contract fields plus:
+A plain run sets up, warms up, times ``--steps`` steps and prints ONE JSON line (rank 0) with
+the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...); the
+fields below are null in it.  ``--dump-outputs DIR`` also writes what the last timed step
+returned (``loss.npy``, ``flow0.npy`` ... as float32; same arguments, same inputs, so two builds
+can be compared output for output).  ``--full`` adds everything else the bench measures:
   roofline      -- dominant kernel (the conv instance with the largest total time) measured
                    with a hipEvent pair around every conv launch of the timed steps, on the
                    stream it is launched on: achieved = algorithmic FLOPs / launch duration,
@@ -310,7 +314,33 @@ def final_parity(pair_np, params, flows_hip, precision="fp32", levels=4):
                     "the last timed step"}
 
 
-def main():
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: all files together stay under this
+
+
+def dump_outputs(dirname, loss, flows, max_bytes=DUMP_MAX_BYTES):
+    """Write what one train step returned to its caller -- the loss and the flows in the
+    order it returns them -- as ``loss.npy`` and ``flow<i>.npy`` (float32) under ``dirname``.
+    When the arrays together would exceed ``max_bytes``, every flow is cut to the same
+    fraction of its elements: a fixed sample (seeded by the level, so it depends on the shapes
+    only) of the flattened array, in index order.  Returns {name: array} as written."""
+    arrays = {"loss": np.asarray(loss.detach().float().cpu().numpy(), np.float32).reshape(1)}
+    flows_np = [np.ascontiguousarray(f.detach().float().cpu().numpy(), dtype=np.float32)
+                for f in flows]
+    budget = max_bytes - 4096 * (1 + len(flows_np))          # .npy headers, the loss
+    total = sum(a.nbytes for a in flows_np)
+    for i, a in enumerate(flows_np):
+        if total > budget:
+            keep = max(1, int(a.size * (budget / total)))
+            idx = np.sort(np.random.default_rng(1000 + i).integers(0, a.size, keep))
+            a = a.reshape(-1)[idx]
+        arrays["flow%d" % i] = a
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return arrays
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -318,7 +348,16 @@ def main():
     ap.add_argument("--height", type=int, default=384)
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--batch", type=int, default=8, help="pairs per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the "
+                         "parity probes against the CPU oracle, the CPU baseline, the per-kernel "
+                         "tables and the dominant kernel's roofline (two more untimed steps and "
+                         "hipEvent pairs in the last --timing-steps timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the loss and flows the last one returned "
+                         "as DIR/<name>.npy (float32, at most 64 MB together)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline and the parity figures it feeds")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--timing-steps", type=int, default=2,
                     help="steps whose conv launches carry hipEvent pairs: the last ones of the "
@@ -347,7 +386,9 @@ def main():
                     default=int(os.environ.get("OFLOW_DETERMINISTIC", "1")),
                     help="1 (default): the deterministic warp backward (window gather / int64 "
                          "fixed point, ops.DETERMINISTIC); 0: the float-atomic warp_bwd_gather")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from optical_flow_amd import _lib, ops
     ops.SIDE_STREAM_WGRAD = bool(args.side_stream)
@@ -377,14 +418,16 @@ def main():
     trainer = Trainer(net, KerasAdam(net.store), LossLayer())
     batch = torch.from_numpy(synthetic_batch(B, H, W, seed=1234, rank=rank)).cuda()
 
-    # ---- parity probe: HIP forward on the whole bench batch with the initial weights -----
-    with torch.no_grad():
-        flows_hip = [f.cpu() for f in net(batch)]
-        loss_hip = float(LossLayer()(batch, [f.cuda() for f in flows_hip]))
+    # ---- parity probe (--full): HIP forward on the whole bench batch with the initial weights
+    if args.full:
+        with torch.no_grad():
+            flows_hip = [f.cpu() for f in net(batch)]
+            loss_hip = float(LossLayer()(batch, [f.cuda() for f in flows_hip]))
 
     # ---- training throughput --------------------------------------------------------------
-    # The roofline timing is taken live in the timed region: over its last --timing-steps
-    # steps each launch of the dominant conv kernel is bracketed by a hipEvent pair on the
+    # A plain run goes from the warm-up straight to the timed steps, with no kernel timing.
+    # With --full the roofline timing is taken live in the timed region: over its last
+    # --timing-steps steps each launch of the dominant conv kernel is bracketed by a hipEvent pair on the
     # stream it is launched on (one-shot of_timing_enable(2) from ops._tag), so its durations
     # are those of the measured run.  Which kernel dominates, and the per-kernel table, come
     # from one untimed step after the warm-up with every conv launch timed (event pairs around
@@ -394,7 +437,7 @@ def main():
     for i in range(args.warmup):
         trainer.train_step(batch, i)
     torch.cuda.synchronize()
-    live = args.roofline_window == "timed"
+    live = args.full and args.roofline_window == "timed"
     prof_per, prof_only, alone = {}, None, {}
     if live:
         ops.TIMING_TAGS = []
@@ -478,6 +521,8 @@ def main():
     if world > 1:     # control plane (gloo); the gradients went over the C-ABI RCCL comm
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, flows)
     pairs = world * B * args.steps
     value = pairs / elapsed
     final_loss = float(loss)
@@ -495,7 +540,8 @@ def main():
 
     # ---- dominant-kernel roofline ------------------------------------------------------------
     nsteps = args.steps - timed_from
-    if not live:   # --roofline-window extra: separate instrumented steps, convs on one stream
+    # --full --roofline-window extra: separate instrumented steps, convs on one stream
+    if args.full and not live:
         nsteps = args.timing_steps
         ops.TIMING_TAGS = []
         ops.SIDE_STREAM_WGRAD = False
@@ -518,7 +564,8 @@ def main():
         per[k] = (tf + flops[i], tm + ms[i], cnt + 1)
     if graphed is not None:          # graph mode: the fully timed eager step (see above)
         per, nsteps = dict(prof_per), 1
-    if os.environ.get("OFLOW_TIMING_DUMP") and rank == 0 and len(tags) == n:
+    if (os.environ.get("OFLOW_TIMING_DUMP") and rank == 0 and tags is not None
+            and len(tags) == n):
         with open(os.environ["OFLOW_TIMING_DUMP"], "w") as f:
             json.dump([{"layer": tags[i][0], "kind": kinds[i], "gflop": flops[i] / 1e9,
                         "ms": ms[i]} for i in range(n)], f)
@@ -581,14 +628,16 @@ def main():
 
     # ---- parity probe at the final weights: HIP forward of one pair (the oracle runs after
     # the timed region, below) -------------------------------------------------------------
-    with torch.no_grad():
-        flows_fin = [f.cpu() for f in net(batch[:1])]
-    params_fin = {k: v.detach().cpu() for k, v in net.store.params.items()}
+    if args.full:
+        with torch.no_grad():
+            flows_fin = [f.cpu() for f in net(batch[:1])]
+        params_fin = {k: v.detach().cpu() for k, v in net.store.params.items()}
 
     # ---- CPU baseline + EPE vs the oracle (rank 0 only) ----------------------------------
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:     # N=1 only (contract)
+    # (N=1 only: contract)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cps, threads, host_cpus, nsteps_cpu, flows_ref, loss_ref = cpu_baseline(
             batch.cpu().numpy(), vals, args.cpu_steps, args.precision, args.levels)
         cpu = {"value": round(cps, 4), "unit": "image-pairs/s", "cores": threads,
@@ -640,7 +689,8 @@ def main():
                        **({"levels": args.levels} if args.levels != 4 else {})},
             "algorithmic_gflop_per_pair": round(gfp, 2),
             "model_tflops": round(gfp * value / 1e3, 2),
-            "conv_ms_per_step": round(conv_ms_step, 3),
+            "full": bool(args.full),
+            "conv_ms_per_step": round(conv_ms_step, 3) if args.full else None,
             "final_loss": final_loss,
             "flow_abs_mean_max": flow_abs,
             "timed_state": timed_state,

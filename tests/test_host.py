@@ -64,6 +64,34 @@ def test_flop_model_matches_survey():
     assert abs(bench.gflop_per_pair(768, 1024) - 999.4) < 0.1
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files of the loss and every flow; over the byte
+    budget, the same fixed sample of every flow on every call."""
+    import os
+
+    import bench
+    g = torch.Generator().manual_seed(0)
+    loss = torch.rand((), generator=g, dtype=torch.float64)
+    flows = [torch.rand(2, 12 >> i, 20 >> i, 2, generator=g) for i in range(3)]
+    a = bench.dump_outputs(str(tmp_path / "a"), loss, flows)
+    assert sorted(os.listdir(tmp_path / "a")) == ["flow0.npy", "flow1.npy", "flow2.npy", "loss.npy"]
+    assert np.load(tmp_path / "a" / "loss.npy") == np.float32(loss.item())
+    for i, f in enumerate(flows):
+        got = np.load(tmp_path / "a" / ("flow%d.npy" % i))
+        assert got.dtype == np.float32 and np.array_equal(got, f.numpy())
+        assert np.array_equal(got, a["flow%d" % i])
+    cap = 4096 * 4 + 1200                         # room for ~300 of the 1260 flow elements
+    b = bench.dump_outputs(str(tmp_path / "b"), loss, flows, max_bytes=cap)
+    c = bench.dump_outputs(str(tmp_path / "c"), loss, [f + 1 for f in flows], max_bytes=cap)
+    size = sum(os.path.getsize(tmp_path / "b" / n) for n in os.listdir(tmp_path / "b"))
+    assert size <= cap
+    for i, f in enumerate(flows):
+        got = np.load(tmp_path / "b" / ("flow%d.npy" % i))
+        assert got.dtype == np.float32 and got.ndim == 1 and 0 < got.size < f.numel()
+        assert np.isin(got, f.numpy()).all()
+        assert np.array_equal(c["flow%d" % i], got + 1)            # the same elements each time
+
+
 def test_synthetic_value_contract():
     from optical_flow_amd.data import IMAGE_MEANS, synthetic_batch
     b = synthetic_batch(2, 32, 48, seed=3)

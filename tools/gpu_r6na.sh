@@ -6,7 +6,7 @@ OUT=${1:-gpurun_out/r6na}
 mkdir -p "$OUT"
 for rnd in 1 2; do
   for k in 0 1; do
-    OFLOW_TUNE=39=$k timeout -k 10 300 python bench.py --no-cpu-baseline > $OUT/bench_k${k}_$rnd.log 2>&1 || { echo "bench k$k failed"; exit 1; }
+    OFLOW_TUNE=39=$k timeout -k 10 300 python bench.py --full --no-cpu-baseline > $OUT/bench_k${k}_$rnd.log 2>&1 || { echo "bench k$k failed"; exit 1; }
     python - $OUT/bench_k${k}_$rnd.log $k <<'PY'
 import json, sys
 j = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -9,7 +9,7 @@ echo "tests rc $r"; grep -E "^FAILED|^E  |passed|failed" $OUT/tests.log | head -
 [ $r -eq 0 ] || exit $r
 for rnd in 1 2 3; do
   for k in 1 0; do
-    OFLOW_SMASK=$k timeout -k 10 300 python bench.py --no-cpu-baseline > $OUT/bench_k${k}_$rnd.log 2>&1 || { echo "bench k$k failed"; tail -3 $OUT/bench_k${k}_$rnd.log; exit 1; }
+    OFLOW_SMASK=$k timeout -k 10 300 python bench.py --full --no-cpu-baseline > $OUT/bench_k${k}_$rnd.log 2>&1 || { echo "bench k$k failed"; tail -3 $OUT/bench_k${k}_$rnd.log; exit 1; }
     python - $OUT/bench_k${k}_$rnd.log $k <<'PY'
 import json, sys
 j = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

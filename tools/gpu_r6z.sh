@@ -10,7 +10,7 @@ echo "tests rc $r"; grep -E "^FAILED|^E  |passed|failed" $OUT/tests.log | head -
 [ $r -eq 0 ] || exit $r
 for rnd in 1 2; do
   for k in $KEYS; do
-    OFLOW_TUNE=36=$k timeout -k 10 300 python bench.py --no-cpu-baseline $BENCH_ARGS > $OUT/bench_k${k}_$rnd.log 2>&1; r=$?
+    OFLOW_TUNE=36=$k timeout -k 10 300 python bench.py --full --no-cpu-baseline $BENCH_ARGS > $OUT/bench_k${k}_$rnd.log 2>&1; r=$?
     [ $r -eq 0 ] || { echo "bench k$k rc $r"; tail -3 $OUT/bench_k${k}_$rnd.log; exit $r; }
     python - $OUT/bench_k${k}_$rnd.log $k <<'PY'
 import json, sys

@@ -14,9 +14,9 @@ j "$IN/bench_cfg5.log" > profiles/${R}_cfg5_bench.json
 cp "$IN/prof/bench_kernel_stats.csv" profiles/${R}_bench_kernel_stats.csv
 cp "$IN/prof_bf16/bench_kernel_stats.csv" profiles/${R}_bf16_bench_kernel_stats.csv
 python tools/make_summary.py "$IN/bench.log" "$IN/prof/bench_kernel_stats.csv" \
-  "python bench.py --no-cpu-baseline" > profiles/${R}_summary.md
+  "python bench.py --full --no-cpu-baseline" > profiles/${R}_summary.md
 python tools/make_summary.py "$IN/bench_bf16.log" "$IN/prof_bf16/bench_kernel_stats.csv" \
-  "python bench.py --precision bf16 --batch 32 --no-cpu-baseline" > profiles/${R}_bf16_summary.md
+  "python bench.py --full --precision bf16 --batch 32 --no-cpu-baseline" > profiles/${R}_bf16_summary.md
 if [ -f "$IN/pmc_traffic.json" ]; then
   cp "$IN/pmc_traffic.json" profiles/pmc_traffic.json
 else
