@@ -343,6 +343,31 @@ int of_photo_l1_bwd_multi(const float* const* img6s, const float* const* flows, 
 int of_sum_partials(const float* const* parts, const int* counts, const float* coefs,
                     int ngroups, float* out, void* stream);
 
+/* Edge-aware first-order flow smoothness, every level in one launch (levels <= 8; level l
+ * holds flows[l] (n,hs[l],ws[l],2) and, when edge_alpha != 0, img6s[l] (n,hs[l],ws[l],6),
+ * whose channels 0..2 are image 1).  With rho(d) = sqrt(d*d + eps) and the edge weight
+ * w(p,q) = exp(-edge_alpha * mean_{c<3} |img[p,c] - img[q,c]|) (1 when edge_alpha == 0; img6s
+ * may then be NULL and no image byte is read),
+ *   Sv = sum over (b, i<h-1, j, c<2) of w((i,j),(i+1,j)) * rho(f[b,i,j,c] - f[b,i+1,j,c])
+ *   Sh = sum over (b, i, j<w-1, c<2) of w((i,j),(i,j+1)) * rho(f[b,i,j,c] - f[b,i,j+1,c]).
+ * Forward: per-block partials, concatenated in level order (the partials-count function
+ * below gives a level's share); level l's slice sums to coefs_v[l]*Sv + coefs_h[l]*Sh, and
+ * of_sum_partials reduces them.  Backward: d(flow) of sum_l (coefs_v[l]*Sv + coefs_h[l]*Sh),
+ * times dloss[0] if dloss; a gather with no atomics; two floats per pixel at row stride lds[l]
+ * (>= 2; further channels of a padded row are not touched), added to what is there when
+ * accumulate != 0, else overwriting.  The images are constants.  OF_EINVAL (and no launch) for
+ * levels outside 1..8, n, h or w < 1, eps <= 0, lds[l] < 2, NULL img6s with edge_alpha != 0. */
+int of_flow_smooth_partials(int n, int h, int w);
+int of_flow_smooth_fwd_multi(const float* const* img6s, const float* const* flows, int n,
+                             const int* hs, const int* ws, int levels, float edge_alpha,
+                             float eps, const float* coefs_v, const float* coefs_h,
+                             float* partials, void* stream);
+int of_flow_smooth_bwd_multi(const float* const* img6s, const float* const* flows, int n,
+                             const int* hs, const int* ws, int levels, float edge_alpha,
+                             float eps, const float* coefs_v, const float* coefs_h,
+                             const float* dloss, float* const* dflows, const int* lds,
+                             int accumulate, void* stream);
+
 /* Keras Adam (train.py:34,56; P13), one launch over a flat parameter arena, g' = g*gscale
  * (gscale folds the 1/world of a data-parallel gradient average):
  * m += (g'-m)(1-b1); v += (g'^2-v)(1-b2); p -= lr_t * m / (sqrt(v) + eps). */

@@ -8,7 +8,24 @@ class LossLayer:
     """Multi-scale photometric L1: for scale s, resize the (B,H,W,6) pairs to H/2^(s+1),
     warp image2 by flows[s] with ``warp_features``' convention, mean |image1 - warped| over
     B*h*w*3, averaged over scales (P10).  HIP: one pyramid kernel per level, one fused
-    warp+|diff|+reduce kernel per scale, and a d(flow) kernel per scale for the backward."""
+    warp+|diff|+reduce kernel per scale, and a d(flow) kernel per scale for the backward.
+
+    ``LossLayer()`` is the reference's layer.  ``smoothness_weight`` > 0 (build-added) adds
+    that weight times the edge-aware first-order smoothness of every scale's flow: the mean
+    Charbonnier penalty sqrt(d^2 + smoothness_eps) of the vertical plus that of the horizontal
+    first differences, each weighted by exp(-edge_alpha * mean |d image1|) across the same
+    pixel pair, averaged over scales (ops.flow_loss; DESIGN.md has the definition)."""
+
+    def __init__(self, smoothness_weight=0.0, edge_alpha=0.0, smoothness_eps=1e-4):
+        if not smoothness_weight >= 0:
+            raise ValueError("smoothness_weight must be >= 0, got %r" % (smoothness_weight,))
+        if not edge_alpha >= 0:
+            raise ValueError("edge_alpha must be >= 0, got %r" % (edge_alpha,))
+        if not smoothness_eps > 0:
+            raise ValueError("smoothness_eps must be > 0, got %r" % (smoothness_eps,))
+        self.smoothness_weight = float(smoothness_weight)
+        self.edge_alpha = float(edge_alpha)
+        self.smoothness_eps = float(smoothness_eps)
 
     def __call__(self, batch_imgs, flows):
         num_scales = len(flows)
@@ -19,4 +36,7 @@ class LossLayer:
             assert flows[scale_idx].shape[1] == scaled_height
             assert flows[scale_idx].shape[2] == scaled_width
         assert batch_imgs.shape[3] == 6
-        return ops.photometric_loss(batch_imgs, list(flows))
+        if self.smoothness_weight == 0.0:
+            return ops.photometric_loss(batch_imgs, list(flows))
+        return ops.flow_loss(batch_imgs, list(flows), self.smoothness_weight, self.edge_alpha,
+                             self.smoothness_eps)

@@ -2156,3 +2156,204 @@ def photometric_loss(batch_imgs, flows):
     if any(fg is not None and fg.shape != tuple(f.shape) for fg, f in zip(fgs, flows)):
         fgs = [None] * len(flows)
     return _PhotoLoss.apply(batch_imgs, fgs, *flows)
+
+
+# ============================================================== flow smoothness =====
+def _arr(ctype, vals):
+    return (ctype * len(vals))(*vals)
+
+
+def _pyramid6(b, flows):
+    """The loss's image pyramid (loss.py:17-18): level k is batch_imgs resized to
+    H/2^(k+1) x W/2^(k+1), which must be flows[k]'s size."""
+    n, H, W, c = b.shape
+    assert c == 6
+    pyr = []
+    for k, f in enumerate(flows):
+        h = int(H / (2.0 ** (k + 1)))
+        w = int(W / (2.0 ** (k + 1)))
+        assert f.shape[1] == h and f.shape[2] == w, \
+            "flow %d has shape %s, expected (B,%d,%d,2)" % (k, tuple(f.shape), h, w)
+        pyr.append(torch.empty((n, h, w, 6), device=b.device))
+    call("of_pyramid6", _ptr(b), n, H, W, len(pyr), _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
+         _stream())
+    return pyr
+
+
+def _smooth_coefs(n, hs, ws, scale):
+    """The normalisers of the smoothness term, times ``scale``: the mean over each
+    direction's pairs and over the levels; a direction with no pairs contributes 0."""
+    ns = len(hs)
+    cv = [scale / (ns * n * (h - 1) * w * 2) if h > 1 else 0.0 for h, w in zip(hs, ws)]
+    ch = [scale / (ns * n * h * (w - 1) * 2) if w > 1 else 0.0 for h, w in zip(hs, ws)]
+    return cv, ch
+
+
+def _smooth_fwd(pyr, fl, edge_alpha, eps, cv, ch):
+    """of_flow_smooth_fwd_multi over every level: the partials (they sum to the weighted
+    term, the coefficients are applied in the kernel)."""
+    ns = len(fl)
+    n = fl[0].shape[0]
+    hs = [f.shape[1] for f in fl]
+    ws_ = [f.shape[2] for f in fl]
+    nparts = sum(_lib.lib().of_flow_smooth_partials(n, h, w) for h, w in zip(hs, ws_))
+    parts = torch.empty(nparts, device=fl[0].device)
+    imgs = _arr(C.c_void_p, [p.data_ptr() for p in pyr]) if edge_alpha != 0 else None
+    call("of_flow_smooth_fwd_multi", imgs, _arr(C.c_void_p, [f.data_ptr() for f in fl]), n,
+         _arr(C.c_int, hs), _arr(C.c_int, ws_), ns, edge_alpha, eps, _arr(C.c_float, cv),
+         _arr(C.c_float, ch), _ptr(parts), _stream())
+    return parts
+
+
+def _smooth_bwd(pyr, flows, lv, edge_alpha, eps, cv, ch, dloss, accumulate):
+    """of_flow_smooth_bwd_multi for the levels in ``lv`` ((level, output, row stride), as
+    _PhotoLoss.backward builds them)."""
+    m = len(lv)
+    n = flows[0].shape[0]
+    imgs = (_arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]) if edge_alpha != 0
+            else None)
+    call("of_flow_smooth_bwd_multi", imgs,
+         _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]), n,
+         _arr(C.c_int, [flows[k].shape[1] for k, _, _ in lv]),
+         _arr(C.c_int, [flows[k].shape[2] for k, _, _ in lv]), m, edge_alpha, eps,
+         _arr(C.c_float, [cv[k] for k, _, _ in lv]), _arr(C.c_float, [ch[k] for k, _, _ in lv]),
+         _ptr(dloss), _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
+         _arr(C.c_int, [ld for _, _, ld in lv]), accumulate, _stream())
+
+
+class _FlowSmooth(torch.autograd.Function):
+    """Edge-aware first-order smoothness of every level's flow (include/oflow.h,
+    of_flow_smooth_fwd_multi): mean over levels of the mean Charbonnier penalty of the
+    vertical plus that of the horizontal first differences, each weighted by
+    exp(-edge_alpha * mean|d image1|) across the same pair.  The images are constants."""
+
+    @staticmethod
+    def forward(ctx, batch_imgs, cfg, *flows):
+        edge_alpha, eps = cfg
+        _check_dev(batch_imgs, *flows)
+        assert 1 <= len(flows) <= 8
+        fl = [f.contiguous() for f in flows]
+        n = fl[0].shape[0]
+        pyr = _pyramid6(batch_imgs.contiguous(), fl) if edge_alpha != 0 else []
+        cv, ch = _smooth_coefs(n, [f.shape[1] for f in fl], [f.shape[2] for f in fl], 1.0)
+        parts = _smooth_fwd(pyr, fl, edge_alpha, eps, cv, ch)
+        out = torch.empty((), device=parts.device)
+        call("of_sum_partials", _arr(C.c_void_p, [parts.data_ptr()]),
+             _arr(C.c_int, [parts.numel()]), _arr(C.c_float, [1.0]), 1, _ptr(out), _stream())
+        ctx.save_for_backward(*pyr, *fl)
+        ctx.cfg = (len(fl), edge_alpha, eps, cv, ch)
+        return out
+
+    @staticmethod
+    def backward(ctx, dloss):
+        ns, edge_alpha, eps, cv, ch = ctx.cfg
+        saved = ctx.saved_tensors
+        pyr, flows = saved[:len(saved) - ns], saved[len(saved) - ns:]
+        dloss = dloss.contiguous()
+        grads, lv = [], []
+        for k in range(ns):
+            if not ctx.needs_input_grad[2 + k]:
+                grads.append(None)
+                continue
+            df = torch.empty_like(flows[k])
+            grads.append(df)
+            lv.append((k, df, 2))
+        if lv:
+            _smooth_bwd(pyr, flows, lv, edge_alpha, eps, cv, ch, dloss, 0)
+        return (None, None, *grads)
+
+
+def flow_smoothness(batch_imgs, flows, edge_alpha=0.0, eps=1e-4):
+    """The smoothness term alone (a scalar; plain gradients for the flows).  The image
+    pyramid is only built when ``edge_alpha`` is not 0."""
+    return _FlowSmooth.apply(batch_imgs, (float(edge_alpha), float(eps)), *flows)
+
+
+class _FlowLoss(torch.autograd.Function):
+    """photometric + smoothness_weight * smoothness, the training loss with the regulariser
+    on: what _PhotoLoss does, then the smoothness forward on the same pyramid tensors.  One
+    Function for both terms because of the FlowGrad protocol: the loss writes a flow's
+    gradient buffer once (of_photo_l1_bwd_multi overwrites, of_flow_smooth_bwd_multi then adds
+    into the same outputs) and upscale_flow's backward adds to it afterwards."""
+
+    @staticmethod
+    def forward(ctx, batch_imgs, fgs, cfg, *flows):
+        weight, edge_alpha, eps = cfg
+        _check_dev(batch_imgs, *flows)
+        ctx.fgs = fgs
+        b = batch_imgs.contiguous()
+        n = b.shape[0]
+        ns = len(flows)
+        assert 1 <= ns <= 7, "of_sum_partials takes 8 groups: 7 levels and the smoothness term"
+        s = _stream()
+        fl = [f.contiguous() for f in flows]
+        pyr = _pyramid6(b, fl)
+        hs = [p.shape[1] for p in pyr]
+        ws_ = [p.shape[2] for p in pyr]
+        nparts = [_lib.lib().of_photo_l1_partials(n, h, w) for h, w in zip(hs, ws_)]
+        coefs = [1.0 / (ns * n * h * w * 3) for h, w in zip(hs, ws_)]
+        parts = torch.empty(sum(nparts), device=b.device)
+        call("of_photo_l1_fwd_multi", _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
+             _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs),
+             _arr(C.c_int, ws_), ns, _ptr(parts), s)
+        cv, ch = _smooth_coefs(n, hs, ws_, weight)
+        sparts = _smooth_fwd(pyr, fl, edge_alpha, eps, cv, ch)
+        offs = [0]
+        for k in range(ns):
+            offs.append(offs[-1] + nparts[k])
+        # the smoothness partials carry their coefficients: one more group, coefficient 1
+        groups = [(parts.data_ptr() + 4 * offs[k], nparts[k], coefs[k]) for k in range(ns)]
+        groups.append((sparts.data_ptr(), sparts.numel(), 1.0))
+        loss = torch.empty((), device=b.device)
+        call("of_sum_partials", _arr(C.c_void_p, [g[0] for g in groups]),
+             _arr(C.c_int, [g[1] for g in groups]), _arr(C.c_float, [g[2] for g in groups]),
+             len(groups), _ptr(loss), s)
+        ctx.save_for_backward(*pyr, *fl)
+        ctx.cfg = (ns, edge_alpha, eps, coefs, cv, ch)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        ns, edge_alpha, eps, coefs, cv, ch = ctx.cfg
+        saved = ctx.saved_tensors
+        pyr, flows = saved[:ns], saved[ns:]
+        dloss = dloss.contiguous()
+        s = _stream()
+        grads, lv = [], []          # lv: (level, output, row stride) of one multi launch
+        for k in range(ns):
+            if not ctx.needs_input_grad[3 + k]:
+                grads.append(None)
+                continue
+            fg = ctx.fgs[k]
+            if fg is not None:         # into the flow head's padded gradient (FlowGrad)
+                buf = fg.buffer()
+                fg.filled = True
+                grads.append(buf[..., :2])
+                lv.append((k, buf, 4))
+                continue
+            df = torch.empty_like(flows[k])
+            grads.append(df)
+            lv.append((k, df, 2))
+        if lv:
+            m = len(lv)
+            n = pyr[0].shape[0]
+            # the photometric gradient writes every output, the smoothness gradient adds
+            call("of_photo_l1_bwd_multi", _arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]),
+                 _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]), n,
+                 _arr(C.c_int, [pyr[k].shape[1] for k, _, _ in lv]),
+                 _arr(C.c_int, [pyr[k].shape[2] for k, _, _ in lv]), m,
+                 _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
+                 _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
+                 _arr(C.c_int, [ld for _, _, ld in lv]), s)
+            _smooth_bwd(pyr, flows, lv, edge_alpha, eps, cv, ch, dloss, 1)
+        return (None, None, None, *grads)
+
+
+def flow_loss(batch_imgs, flows, smoothness_weight, edge_alpha=0.0, eps=1e-4):
+    """The training loss with the smoothness regulariser: photometric_loss plus
+    ``smoothness_weight`` times flow_smoothness, in one Function (see _FlowLoss)."""
+    fgs = [getattr(f, "_of_flowgrad", None) for f in flows]
+    if any(fg is not None and fg.shape != tuple(f.shape) for fg, f in zip(fgs, flows)):
+        fgs = [None] * len(flows)
+    return _FlowLoss.apply(batch_imgs, fgs,
+                           (float(smoothness_weight), float(edge_alpha), float(eps)), *flows)

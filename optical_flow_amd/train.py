@@ -237,6 +237,10 @@ def main(argv=None):
     ap.add_argument("--kitti", default=None, help="KITTI raw root (train.py:20)")
     ap.add_argument("--nworkers", type=int, default=6)      # train.py:22
     ap.add_argument("--display-dir", default=None, help="PNG flow pictures every 10 batches")
+    ap.add_argument("--smoothness-weight", type=float, default=0.0,
+                    help="weight of the edge-aware flow smoothness term (0: the reference loss)")
+    ap.add_argument("--edge-alpha", type=float, default=0.0,
+                    help="edge sensitivity of the smoothness term (0: unweighted)")
     args = ap.parse_args(argv)
 
     rank, world, local = init_from_env()
@@ -245,8 +249,12 @@ def main(argv=None):
     if rank == 0:
         net.summary()
     opt = KerasAdam(net.store, learning_rate=args.lr)
-    trainer = Trainer(net, opt)
+    trainer = Trainer(net, opt, LossLayer(args.smoothness_weight, args.edge_alpha))
     log = open(args.log, "a") if (args.log and rank == 0) else None
+    if log and (args.smoothness_weight or args.edge_alpha):
+        # header record (no "step" key); a default run's log holds step records only, as before
+        log.write(json.dumps({"header": True, "smoothness_weight": args.smoothness_weight,
+                              "edge_alpha": args.edge_alpha}) + "\n")
     reader = None
     if args.kitti:
         from .data_reader import AsyncReader, ReaderOpts

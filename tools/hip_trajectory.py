@@ -1,6 +1,7 @@
 """Training trajectory of the HIP path from bench.py's exact start (GPU).
 
 python tools/hip_trajectory.py --steps 26 [--det] [--precision fp32] --out gpurun_out/traj.jsonl
+    [--smoothness-weight 0.2 --edge-alpha 10]      (the loss with the smoothness term on)
 
 Same weights, batch and optimizer as bench.py and tools/oracle_trajectory.py; one JSON line
 per step: loss and mean / max |flow| per level of that step's forward (the weights before the
@@ -30,6 +31,8 @@ def main():
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--det", action="store_true")
     ap.add_argument("--oracle-every", type=int, default=0)
+    ap.add_argument("--smoothness-weight", type=float, default=0.0)
+    ap.add_argument("--edge-alpha", type=float, default=0.0)
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     from optical_flow_amd import _lib, ops
@@ -43,13 +46,17 @@ def main():
     H, W, B = args.height, args.width, args.batch
     vals = init_params(flow_net_spec(levels=4), 0)
     net = FlowNet(H, W, values=vals, precision=args.precision)
-    trainer = Trainer(net, KerasAdam(net.store), LossLayer())
+    trainer = Trainer(net, KerasAdam(net.store),
+                      LossLayer(args.smoothness_weight, args.edge_alpha))
     batch_np = synthetic_batch(B, H, W, seed=1234)
     batch = torch.from_numpy(batch_np).cuda()
     blocks = list(encoder_blocks(4))
     with open(args.out, "w") as f:
         for s in range(args.steps):
             rec = {"step": s, "det": args.det, "precision": args.precision}
+            if args.smoothness_weight:
+                rec.update({"smoothness_weight": args.smoothness_weight,
+                            "edge_alpha": args.edge_alpha})
             if args.oracle_every and s % args.oracle_every == 0:
                 from oracle import ref_flow as R
                 p = {k: v.detach().double().cpu() for k, v in net.store.params.items()}
