@@ -577,6 +577,45 @@ int of_reader_destroy(of_reader* r);
 int of_preprocess_pairs(const void* dev_raw, int npairs, int out_h, int out_w, float* out,
                         void* stream);
 
+/* Training augmentation (build-added; the reference stops at "# TODO: Data augmentation",
+ * train.py:13): random zoom / crop, horizontal flip, rotation and colour jitter of a raw batch,
+ * in the one kernel that otherwise resizes it.  The host draws one record per pair
+ * (optical_flow_amd/data_reader.py, sample_augment); both images of the pair share it. */
+typedef struct of_augment {      /* 64 bytes */
+  float m[6];        /* u = (m0*xc + m1*yc) + m2,  v = (m3*xc + m4*yc) + m5,  xc = x+0.5, yc = y+0.5:
+                        output pixel centre -> NORMALISED source position, (0,0)-(1,1) = whole frame */
+  float gain[3];     /* per-channel multiplier, B G R */
+  float brightness;  /* added */
+  float contrast;    /* about 0.5 */
+  float saturation;  /* about the pixel's gray */
+  int32_t flags;     /* bit 0: run the colour stage */
+  int32_t pad[3];
+} of_augment;
+/* Raw batch in device memory (the layout of_preprocess_pairs reads) + npairs records in device
+ * memory -> (npairs, out_h, out_w, 6) float32.  Per output pixel (x, y) of pair b and each of
+ * its two images (own size sh x sw), all in float32 in this order, no contraction, correctly
+ * rounded division (tests/augment_np.py restates it bit for bit):
+ *   u, v as above;  sx = u*(float)sw - 0.5f, sy = v*(float)sh - 0.5f, clamped to [0, sw-1] /
+ *   [0, sh-1] (border replication);  x0 = floor(sx), x1 = min(x0+1, sw-1), fx = sx - x0 (same
+ *   for y);  per channel on the 8-bit taps as float: top = p00 + (p01-p00)*fx,
+ *   bot = p10 + (p11-p10)*fx, val = (top + (bot-top)*fy) / 255;
+ *   if flags & 1: val *= gain[c]; val += brightness; val = (val-0.5)*contrast + 0.5; then with
+ *   the three channels at that point gray = (0.114 B + 0.587 G) + 0.299 R,
+ *   val = gray + (val-gray)*saturation, val = min(max(val, 0), 1);
+ *   out = (float)((double)val - mean[c]), the means of of_preprocess_pairs.
+ * A frame with h <= 0 or w <= 0 gives val = 0 (no colour stage).  The taps stay inside the
+ * frame for any record, finite or not.  OF_EINVAL (and no launch) for a NULL pointer,
+ * npairs < 0 or > 65535, out_h or out_w < 1 or out_h*out_w >= 2^31 - 256. */
+int of_augment_pairs(const void* dev_raw, int npairs, int out_h, int out_w,
+                     const of_augment* dev_params, float* out, void* stream);
+/* of_reader_next with of_augment_pairs in place of of_preprocess_pairs.  host_params: `batch`
+ * records in ordinary host memory (copied into the slot's pinned staging area before the call
+ * returns); dev_params: `batch` records of device scratch, written by an asynchronous copy on
+ * `stream` ahead of the launch.  No synchronisation is added. */
+int of_reader_next_aug(of_reader* r, void* dev_raw, int64_t cap, const of_augment* host_params,
+                       of_augment* dev_params, float* out, int out_h, int out_w,
+                       int32_t* pair_index, int32_t* swapped, void* stream);
+
 /* ==== SURVEY.md §8 f row 2: TensorFlow checkpoint bundles (save_weights / load_weights) ===== */
 
 /* CRC32C (Castagnoli) of n bytes, continuing from crc (0 to start; unmasked).  The bundle's

@@ -144,6 +144,9 @@ PROTOTYPES = {
     "of_reader_next_host": (I, [P, P, I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "of_reader_destroy": (I, [P]),
     "of_preprocess_pairs": (I, [P, I, I, I, P, P]),
+    "of_augment_pairs": (I, [P, I, I, I, P, P, P]),
+    "of_reader_next_aug": (I, [P, P, I64, P, P, P, I, I, C.POINTER(C.c_int32),
+                               C.POINTER(C.c_int32), P]),
     "of_flow_color": (I, [P, I, I, I, P, P, P]),
     "of_flow_intensity": (I, [P, I64, P, P]),
     "of_crc32c": (C.c_uint32, [P, I64, C.c_uint32]),   # checkpoint bundles (row 2)

@@ -35,6 +35,8 @@
 namespace oflow {
 int launch_preprocess_pairs(const void* dev_raw, int npairs, int out_h, int out_w, float* out,
                             hipStream_t s);
+int launch_augment_pairs(const void* dev_raw, int npairs, int out_h, int out_w,
+                         const of_augment* dev_params, float* out, hipStream_t s);
 }
 
 using namespace oflow;
@@ -45,7 +47,8 @@ constexpr size_t kAlign = 256;
 inline size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 
 struct Slot {
-  uint8_t* buf = nullptr;      // header (of_image_desc[2B]) + 2B image regions
+  uint8_t* buf = nullptr;      // header (of_image_desc[2B]) + 2B image regions, then the
+                               // staging area of of_reader_next_aug (of_augment[B])
   hipEvent_t copied = nullptr; // recorded after the H2D copy that last read this slot
   bool wait_copy = false;
   int64_t seq = -1;            // batch sequence number held / being decoded
@@ -66,7 +69,7 @@ struct of_reader {
   std::vector<std::string> p1, p2;
   int batch = 0, nslots = 0, max_h = 0, max_w = 0;
   bool pinned = false;
-  size_t header = 0, stride = 0, bytes = 0;
+  size_t header = 0, stride = 0, bytes = 0;   // bytes: the raw batch (what is copied to HBM)
   std::mt19937_64 rng;
   std::vector<int> order;
   int nbatches = 0, next_batch_idx = 0;
@@ -240,21 +243,22 @@ int of_reader_create(int npairs, const char* const* path1, const char* const* pa
   for (auto& s : r->slots) {
     s.pair.resize(batch);
     s.swapped.resize(batch);
+    const size_t alloc = r->bytes + align_up(sizeof(of_augment) * batch);
     if (r->pinned) {
-      if (hipHostMalloc(reinterpret_cast<void**>(&s.buf), r->bytes, hipHostMallocDefault) != hipSuccess ||
+      if (hipHostMalloc(reinterpret_cast<void**>(&s.buf), alloc, hipHostMallocDefault) != hipSuccess ||
           hipEventCreateWithFlags(&s.copied, hipEventDisableTiming) != hipSuccess) {
         s.buf = nullptr;
         delete r;
         return fail(OF_EHIP, "reader_create: pinned slot allocation failed");
       }
     } else {
-      s.buf = static_cast<uint8_t*>(malloc(r->bytes));
+      s.buf = static_cast<uint8_t*>(malloc(alloc));
       if (!s.buf) {
         delete r;
         return fail(OF_EINVAL, "reader_create: out of host memory");
       }
     }
-    memset(s.buf, 0, r->bytes);
+    memset(s.buf, 0, alloc);
   }
   {
     std::lock_guard<std::mutex> lk(r->mu);
@@ -295,14 +299,14 @@ int of_reader_next_host(of_reader* r, void* dst, int64_t cap, int32_t* pair_inde
   return OF_OK;
 }
 
-int of_reader_next(of_reader* r, void* dev_raw, int64_t cap, float* out, int out_h, int out_w,
-                   int32_t* pair_index, int32_t* swapped, void* stream) {
-  OF_CHECK_ARG(r && dev_raw && out, "reader_next: null argument");
-  OF_CHECK_ARG(r->pinned, "reader_next: the reader was created without pinned slots "
-               "(use of_reader_next_host)");
-  OF_CHECK_ARG(cap >= (int64_t)r->bytes, "reader_next: device buffer smaller than "
-               "of_reader_raw_bytes()");
-  OF_CHECK_ARG(out_h > 0 && out_w > 0, "reader_next: bad output size");
+// of_reader_next (host_params == nullptr) and of_reader_next_aug.  The augment records go
+// through the slot's staging area: like the frames, it is not rewritten before the slot's
+// `copied` event has passed (a slot is handed out again only after its workers, who wait on
+// that event, have refilled it).
+static int reader_next(const char* who, of_reader* r, void* dev_raw, int64_t cap,
+                       const of_augment* host_params, of_augment* dev_params, float* out,
+                       int out_h, int out_w, int32_t* pair_index, int32_t* swapped, void* stream) {
+  const std::string w(who);
   hipStream_t st = as_stream(stream);
   std::unique_lock<std::mutex> lk(r->mu);
   const int s = r->wait_next(lk);
@@ -315,16 +319,50 @@ int of_reader_next(of_reader* r, void* dev_raw, int64_t cap, float* out, int out
     return fail(OF_EINVAL, e);
   }
   if (hipMemcpyAsync(dev_raw, sl.buf, r->bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-    return fail(OF_EHIP, "reader_next: hipMemcpyAsync failed");
-  int rc = launch_preprocess_pairs(dev_raw, r->batch, out_h, out_w, out, st);
+    return fail(OF_EHIP, w + ": hipMemcpyAsync failed");
+  int rc;
+  if (host_params) {
+    const size_t n = sizeof(of_augment) * r->batch;
+    memcpy(sl.buf + r->bytes, host_params, n);
+    if (hipMemcpyAsync(dev_params, sl.buf + r->bytes, n, hipMemcpyHostToDevice, st) != hipSuccess)
+      return fail(OF_EHIP, w + ": hipMemcpyAsync failed");
+    rc = launch_augment_pairs(dev_raw, r->batch, out_h, out_w, dev_params, out, st);
+  } else {
+    rc = launch_preprocess_pairs(dev_raw, r->batch, out_h, out_w, out, st);
+  }
   if (rc != OF_OK) return rc;
-  if (hipEventRecord(sl.copied, st) != hipSuccess) return fail(OF_EHIP, "reader_next: hipEventRecord failed");
+  if (hipEventRecord(sl.copied, st) != hipSuccess) return fail(OF_EHIP, w + ": hipEventRecord failed");
   if (pair_index) std::copy(sl.pair.begin(), sl.pair.end(), pair_index);
   if (swapped) std::copy(sl.swapped.begin(), sl.swapped.end(), swapped);
   sl.wait_copy = true;
   ++r->consumed;
   r->submit(s);
   return OF_OK;
+}
+
+int of_reader_next(of_reader* r, void* dev_raw, int64_t cap, float* out, int out_h, int out_w,
+                   int32_t* pair_index, int32_t* swapped, void* stream) {
+  OF_CHECK_ARG(r && dev_raw && out, "reader_next: null argument");
+  OF_CHECK_ARG(r->pinned, "reader_next: the reader was created without pinned slots "
+               "(use of_reader_next_host)");
+  OF_CHECK_ARG(cap >= (int64_t)r->bytes, "reader_next: device buffer smaller than "
+               "of_reader_raw_bytes()");
+  OF_CHECK_ARG(out_h > 0 && out_w > 0, "reader_next: bad output size");
+  return reader_next("reader_next", r, dev_raw, cap, nullptr, nullptr, out, out_h, out_w,
+                     pair_index, swapped, stream);
+}
+
+int of_reader_next_aug(of_reader* r, void* dev_raw, int64_t cap, const of_augment* host_params,
+                       of_augment* dev_params, float* out, int out_h, int out_w,
+                       int32_t* pair_index, int32_t* swapped, void* stream) {
+  OF_CHECK_ARG(r && dev_raw && host_params && dev_params && out, "reader_next_aug: null argument");
+  OF_CHECK_ARG(r->pinned, "reader_next_aug: the reader was created without pinned slots");
+  OF_CHECK_ARG(cap >= (int64_t)r->bytes, "reader_next_aug: device buffer smaller than "
+               "of_reader_raw_bytes()");
+  OF_CHECK_ARG(out_h > 0 && out_w > 0 && (int64_t)out_h * out_w <= 0x7fffffff - 256,
+               "reader_next_aug: bad output size");
+  return reader_next("reader_next_aug", r, dev_raw, cap, host_params, dev_params, out, out_h,
+                     out_w, pair_index, swapped, stream);
 }
 
 int of_reader_destroy(of_reader* r) {

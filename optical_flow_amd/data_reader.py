@@ -12,10 +12,15 @@ Differences from the reference, by design:
     completion order with unseeded ``random`` / ``np.random``.
   - Worker threads in one process instead of a ``multiprocessing.Pool`` (no cv2 fork issue to
     work around: ``data_reader.py:104-106``).
+  - Seeded training augmentation (``AugmentOpts`` / ``ReaderOpts(augment=...)``; the reference
+    stops at ``# TODO: Data augmentation``, ``train.py:13``): random zoom / crop, horizontal
+    flip, rotation and colour jitter, in the HIP kernel that otherwise does the resize
+    (``augment.hip``).  Off by default.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import List, Optional, Sequence
 
@@ -60,13 +65,131 @@ def read_kitti(kitti_path: str) -> List[List[str]]:
     return pairs
 
 
+# of_augment (include/oflow.h): one 64-byte record per pair
+AUGMENT_DTYPE = np.dtype([("m", np.float32, (6,)), ("gain", np.float32, (3,)),
+                          ("brightness", np.float32), ("contrast", np.float32),
+                          ("saturation", np.float32), ("flags", np.int32),
+                          ("pad", np.int32, (3,))])
+assert AUGMENT_DTYPE.itemsize == 64
+
+
+def _range(name, v, lo_min=None):
+    try:
+        lo, hi = (float(x) for x in v)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a (lo, hi) pair, got %r" % (name, v))
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError("%s must be finite, got %r" % (name, v))
+    if lo > hi:
+        raise ValueError("%s needs lo <= hi, got %r" % (name, v))
+    if lo_min is not None and lo < lo_min:
+        raise ValueError("%s must start at >= %g, got %r" % (name, lo_min, v))
+    return lo, hi
+
+
+def _amplitude(name, v):
+    v = float(v)
+    if not (math.isfinite(v) and v >= 0):
+        raise ValueError("%s must be finite and >= 0, got %r" % (name, v))
+    return v
+
+
+class AugmentOpts:
+    """Training augmentation of the KITTI batch (sample_augment draws from these; both images of
+    a pair get the same draw):
+      zoom         range of z >= 1; the crop window is 1/z of the frame on each axis
+      translate    window position uniform over the slack the zoom leaves (else centred)
+      hflip_prob   probability of a horizontal flip
+      rotate_deg   angle uniform in +-that, about the output centre, in output-pixel space
+                   (samples that leave the frame replicate its border)
+      brightness   delta uniform in +-that, added to the [0, 1] pixel value
+      contrast     range of the factor about 0.5
+      saturation   range of the factor about the pixel's gray
+      color_gain   range of the per-channel multiplier, drawn per channel
+    Every default is the identity; ValueError for a range with lo > hi, zoom below 1, a
+    probability outside [0, 1] or a non-finite value."""
+
+    def __init__(self, zoom=(1.0, 1.0), translate=True, hflip_prob=0.0, rotate_deg=0.0,
+                 brightness=0.0, contrast=(1.0, 1.0), saturation=(1.0, 1.0),
+                 color_gain=(1.0, 1.0)):
+        self.zoom = _range("zoom", zoom, lo_min=1.0)
+        self.translate = bool(translate)
+        hflip_prob = float(hflip_prob)
+        if not 0.0 <= hflip_prob <= 1.0:                  # refuses NaN too
+            raise ValueError("hflip_prob must be in [0, 1], got %r" % (hflip_prob,))
+        self.hflip_prob = hflip_prob
+        self.rotate_deg = _amplitude("rotate_deg", rotate_deg)
+        self.brightness = _amplitude("brightness", brightness)
+        self.contrast = _range("contrast", contrast)
+        self.saturation = _range("saturation", saturation)
+        self.color_gain = _range("color_gain", color_gain)
+
+    @property
+    def has_color(self) -> bool:
+        """Some colour range is non-trivial (the records then carry flags bit 0)."""
+        return (self.brightness != 0.0 or self.contrast != (1.0, 1.0) or
+                self.saturation != (1.0, 1.0) or self.color_gain != (1.0, 1.0))
+
+    def as_dict(self):
+        return {"zoom": list(self.zoom), "translate": self.translate,
+                "hflip_prob": self.hflip_prob, "rotate_deg": self.rotate_deg,
+                "brightness": self.brightness, "contrast": list(self.contrast),
+                "saturation": list(self.saturation), "color_gain": list(self.color_gain)}
+
+
+def sample_augment(opts: AugmentOpts, batch_size: int, out_h: int, out_w: int, seed: int,
+                   batch_index: int) -> np.ndarray:
+    """The of_augment records of one batch: a (batch_size,) array of AUGMENT_DTYPE.
+
+    Draws from ``np.random.default_rng([seed, batch_index])``, so batch k's records depend on
+    (seed, k) alone.  Every draw below is made for every batch, used or not, in this order,
+    each a vector over the batch: zoom z; window position tx, ty in [0, 1); flip (a uniform
+    number < hflip_prob); angle; brightness; contrast; saturation; colour gain (batch x 3).
+
+    The map from the output pixel centre (xc, yc) to the normalised source position is built in
+    float64 and cast to float32 at the end: centre (xc - W/2, yc - H/2), flip (x -> -x), rotate
+    by the angle, scale by 1/z, translate by the window centre (W/(2z) + tx W (1 - 1/z), the
+    same in y; tx = ty = 0.5 without ``translate``), divide by (W, H)."""
+    B, W, H = int(batch_size), float(out_w), float(out_h)
+    rng = np.random.default_rng([int(seed), int(batch_index)])
+    z = rng.uniform(opts.zoom[0], opts.zoom[1], B)
+    tx, ty = rng.uniform(0.0, 1.0, B), rng.uniform(0.0, 1.0, B)
+    flip = rng.uniform(0.0, 1.0, B) < opts.hflip_prob
+    ang = np.deg2rad(rng.uniform(-opts.rotate_deg, opts.rotate_deg, B))
+    bright = rng.uniform(-opts.brightness, opts.brightness, B)
+    contrast = rng.uniform(opts.contrast[0], opts.contrast[1], B)
+    sat = rng.uniform(opts.saturation[0], opts.saturation[1], B)
+    gain = rng.uniform(opts.color_gain[0], opts.color_gain[1], (B, 3))
+    if not opts.translate:
+        tx = ty = np.full(B, 0.5)
+    sgn = np.where(flip, -1.0, 1.0)
+    c, s = np.cos(ang), np.sin(ang)
+    # rows of (rotation x flip) / z, then the centre shift and the window centre
+    a00, a01 = c * sgn / z, -s / z
+    a10, a11 = s * sgn / z, c / z
+    cx = W / (2.0 * z) + tx * (W * (1.0 - 1.0 / z))
+    cy = H / (2.0 * z) + ty * (H * (1.0 - 1.0 / z))
+    a02 = a00 * (-W / 2.0) + a01 * (-H / 2.0) + cx
+    a12 = a10 * (-W / 2.0) + a11 * (-H / 2.0) + cy
+    rec = np.zeros(B, AUGMENT_DTYPE)
+    rec["m"] = np.stack([a00 / W, a01 / W, a02 / W, a10 / H, a11 / H, a12 / H], 1)
+    rec["gain"] = gain
+    rec["brightness"] = bright
+    rec["contrast"] = contrast
+    rec["saturation"] = sat
+    rec["flags"] = 1 if opts.has_color else 0
+    return rec
+
+
 class ReaderOpts:
     """data_reader.py:72-78, plus the build's knobs: seed (shuffle + swaps), nslots (batches
     decoded ahead), pairs (an explicit pair list instead of scanning kitti_path), max_h /
-    max_w (frame size bound; scanned from the PNG headers when None)."""
+    max_w (frame size bound; scanned from the PNG headers when None), augment (an AugmentOpts:
+    get_batch() then augments each batch with records drawn from (seed, batch number); None:
+    the plain resize)."""
 
     def __init__(self, kitti_path, batch_size, img_height, img_width, nworkers, seed=0,
-                 nslots=3, pairs=None, max_h=None, max_w=None):
+                 nslots=3, pairs=None, max_h=None, max_w=None, augment=None):
         self.kitti_path = kitti_path
         self.batch_size = batch_size
         self.img_height = img_height
@@ -77,6 +200,7 @@ class ReaderOpts:
         self.pairs = pairs
         self.max_h = max_h
         self.max_w = max_w
+        self.augment = augment
 
 
 def _cstrings(paths: Sequence[str]):
@@ -153,6 +277,9 @@ class AsyncReader:
         self._copy_stream = None
         self.last_pairs = np.zeros(opts.batch_size, np.int32)
         self.last_swapped = np.zeros(opts.batch_size, np.int32)
+        self.last_augment = None          # the last batch's of_augment records (augment only)
+        self._aug_dev = None
+        self._batches = 0                 # get_batch() calls so far: sample_augment's batch_index
 
     def __enter__(self):
         return self
@@ -188,6 +315,8 @@ class AsyncReader:
         if self._copy_stream is None:
             self._copy_stream = torch.cuda.Stream()
             self._raw_dev = torch.empty(self.raw_bytes, dtype=torch.uint8, device="cuda")
+        if o.augment is not None:
+            return self._get_batch_augmented()
         compute = torch.cuda.current_stream()
         cs = self._copy_stream
         # the raw buffer is reused: order this copy after the previous preprocess (same
@@ -201,11 +330,34 @@ class AsyncReader:
         out.record_stream(compute)
         return out
 
+    def _get_batch_augmented(self) -> torch.Tensor:
+        """get_batch() with of_reader_next_aug: the same ordering on the copy stream, plus the
+        batch's records (kept in last_augment) copied ahead of the kernel from the slot's
+        pinned staging area."""
+        o = self.opts
+        if self._aug_dev is None:
+            self._aug_dev = torch.empty(o.batch_size * AUGMENT_DTYPE.itemsize, dtype=torch.uint8,
+                                        device="cuda")
+        rec = sample_augment(o.augment, o.batch_size, o.img_height, o.img_width, o.seed,
+                             self._batches)
+        self._batches += 1
+        self.last_augment = rec
+        compute = torch.cuda.current_stream()
+        cs = self._copy_stream
+        with torch.cuda.stream(cs):
+            out = torch.empty((o.batch_size, o.img_height, o.img_width, 6), device="cuda")
+            call("of_reader_next_aug", self._r, C.c_void_p(self._raw_dev.data_ptr()),
+                 self.raw_bytes, rec.ctypes.data_as(C.c_void_p),
+                 C.c_void_p(self._aug_dev.data_ptr()), C.c_void_p(out.data_ptr()), o.img_height,
+                 o.img_width, *self._meta(), C.c_void_p(cs.cuda_stream))
+        compute.wait_stream(cs)
+        out.record_stream(compute)
+        return out
 
-def preprocess_frames(frames, out_h: int, out_w: int) -> torch.Tensor:
-    """read_batch (data_reader.py:35-42) for frames already decoded to host memory:
-    [(img1_bgr_u8, img2_bgr_u8), ...] -> (B, out_h, out_w, 6) CUDA tensor (one upload of the
-    raw frames, then of_preprocess_pairs)."""
+
+def _pack_raw(frames) -> np.ndarray:
+    """[(img1_bgr_u8, img2_bgr_u8), ...] -> a raw batch buffer (of_image_desc header + frames,
+    256-byte aligned: the layout the reader's slots hold)."""
     n = len(frames)
     header = -(-16 * 2 * n // 256) * 256
     offs, sizes, total = [], [], header
@@ -222,10 +374,34 @@ def preprocess_frames(frames, out_h: int, out_w: int) -> torch.Tensor:
         desc[k, 1:2].view(np.int32)[:] = (h, w)
         img = frames[k // 2][k % 2]
         raw[off:off + img.nbytes] = np.ascontiguousarray(img).reshape(-1)
+    return raw
+
+
+def preprocess_frames(frames, out_h: int, out_w: int) -> torch.Tensor:
+    """read_batch (data_reader.py:35-42) for frames already decoded to host memory:
+    [(img1_bgr_u8, img2_bgr_u8), ...] -> (B, out_h, out_w, 6) CUDA tensor (one upload of the
+    raw frames, then of_preprocess_pairs)."""
+    n = len(frames)
+    raw = _pack_raw(frames)
     dev = torch.from_numpy(raw).cuda()
     out = torch.empty((n, out_h, out_w, 6), device="cuda")
     call("of_preprocess_pairs", C.c_void_p(dev.data_ptr()), n, out_h, out_w,
          C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return out
+
+
+def augment_frames(frames, out_h: int, out_w: int, params: np.ndarray) -> torch.Tensor:
+    """preprocess_frames with of_augment_pairs: ``params`` is a (len(frames),) array of
+    AUGMENT_DTYPE (sample_augment's result, or records written by hand)."""
+    n = len(frames)
+    params = np.ascontiguousarray(params, dtype=AUGMENT_DTYPE).reshape(-1)
+    assert params.shape[0] == n, "one of_augment record per pair"
+    dev = torch.from_numpy(_pack_raw(frames)).cuda()
+    prm = torch.from_numpy(params.view(np.uint8)).cuda()
+    out = torch.empty((n, out_h, out_w, 6), device="cuda")
+    call("of_augment_pairs", C.c_void_p(dev.data_ptr()), n, out_h, out_w,
+         C.c_void_p(prm.data_ptr()), C.c_void_p(out.data_ptr()),
+         C.c_void_p(torch.cuda.current_stream().cuda_stream))
     return out
 
 

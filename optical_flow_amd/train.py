@@ -8,10 +8,12 @@ normalised), otherwise synthetic pairs with the reference value contract (data.p
 ``--display-dir`` writes the every-10-batches display_training pictures (train.py:80-81) as
 PNGs.  No TensorBoard writer (a JSONL step log instead).  Data parallelism (one process per
 GPU, RCCL all-reduce of gradient buckets overlapped with the backward) is build-added; with
-KITTI each rank reads its own seeded shuffle.
+KITTI each rank reads its own seeded shuffle.  ``--augment`` (KITTI only) switches on the
+seeded GPU augmentation of data_reader.AugmentOpts: random zoom / crop, flip, colour jitter.
 
 Run:  python -m optical_flow_amd.train --height 384 --width 512 --batch 8 --steps 20
       python -m optical_flow_amd.train --kitti /data/kitti_raw --epochs 20
+      python -m optical_flow_amd.train --kitti /data/kitti_raw --epochs 20 --augment
 """
 from __future__ import annotations
 
@@ -221,7 +223,40 @@ class GraphedStep:
         return self.loss, self.flows
 
 
-def main(argv=None):
+# --augment: zoom 1-1.3 with translation, hflip 0.5, brightness +-0.1, contrast, saturation
+# 0.8-1.2, colour gain 0.9-1.1 (no rotation)
+AUGMENT_PRESET = dict(zoom=(1.0, 1.3), translate=True, hflip_prob=0.5, rotate_deg=0.0,
+                      brightness=0.1, contrast=(0.8, 1.2), saturation=(0.8, 1.2),
+                      color_gain=(0.9, 1.1))
+
+
+def augment_from_args(args):
+    """The AugmentOpts of the command line: None without any augmentation flag; --augment is
+    AUGMENT_PRESET; each --aug-* override replaces one field of the preset, or of the identity
+    when --augment is not given.  ValueError (AugmentOpts) for a bad value."""
+    from .data_reader import AugmentOpts
+    over = {}
+    if args.aug_zoom_max is not None:
+        over["zoom"] = (1.0, args.aug_zoom_max)
+    if args.aug_hflip is not None:
+        over["hflip_prob"] = args.aug_hflip
+    if args.aug_rotate is not None:
+        over["rotate_deg"] = args.aug_rotate
+    if args.aug_brightness is not None:
+        over["brightness"] = args.aug_brightness
+    for name, key in (("aug_contrast", "contrast"), ("aug_saturation", "saturation"),
+                      ("aug_color_gain", "color_gain")):
+        a = getattr(args, name)
+        if a is not None:
+            over[key] = (1.0 - a, 1.0 + a)
+    if not args.augment and not over:
+        return None
+    kw = dict(AUGMENT_PRESET) if args.augment else {}
+    kw.update(over)
+    return AugmentOpts(**kw)
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--height", type=int, default=192)       # train.py:15
     ap.add_argument("--width", type=int, default=640)        # train.py:16
@@ -241,7 +276,40 @@ def main(argv=None):
                     help="weight of the edge-aware flow smoothness term (0: the reference loss)")
     ap.add_argument("--edge-alpha", type=float, default=0.0,
                     help="edge sensitivity of the smoothness term (0: unweighted)")
+    g = ap.add_argument_group(
+        "augmentation (with --kitti only)", "seeded by --seed; both images of a pair get the "
+        "same draw; an --aug-* flag without --augment starts from no augmentation")
+    g.add_argument("--augment", action="store_true",
+                   help="preset: zoom 1-1.3 with random crop position, horizontal flip p=0.5, "
+                        "brightness +-0.1, contrast 0.8-1.2, saturation 0.8-1.2, per-channel "
+                        "colour gain 0.9-1.1")
+    g.add_argument("--aug-zoom-max", type=float, default=None, metavar="Z",
+                   help="zoom uniform in [1, Z]; the crop is 1/zoom of the frame per axis")
+    g.add_argument("--aug-hflip", type=float, default=None, metavar="P",
+                   help="probability of a horizontal flip")
+    g.add_argument("--aug-rotate", type=float, default=None, metavar="DEG",
+                   help="rotation uniform in +-DEG about the image centre (preset: 0)")
+    g.add_argument("--aug-brightness", type=float, default=None, metavar="D",
+                   help="brightness delta uniform in +-D (pixel values in [0, 1])")
+    g.add_argument("--aug-contrast", type=float, default=None, metavar="A",
+                   help="contrast factor uniform in [1-A, 1+A]")
+    g.add_argument("--aug-saturation", type=float, default=None, metavar="A",
+                   help="saturation factor uniform in [1-A, 1+A]")
+    g.add_argument("--aug-color-gain", type=float, default=None, metavar="A",
+                   help="per-channel gain uniform in [1-A, 1+A]")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
+    try:
+        augment = augment_from_args(args)
+    except ValueError as e:
+        ap.error(str(e))
+    if augment is not None and not args.kitti:
+        ap.error("--augment / --aug-* apply only with --kitti: without it the driver trains on "
+                 "synthetic pairs, which are not augmented")
 
     rank, world, local = init_from_env()
     torch.cuda.set_device(local)
@@ -251,15 +319,18 @@ def main(argv=None):
     opt = KerasAdam(net.store, learning_rate=args.lr)
     trainer = Trainer(net, opt, LossLayer(args.smoothness_weight, args.edge_alpha))
     log = open(args.log, "a") if (args.log and rank == 0) else None
-    if log and (args.smoothness_weight or args.edge_alpha):
+    if log and (args.smoothness_weight or args.edge_alpha or augment is not None):
         # header record (no "step" key); a default run's log holds step records only, as before
-        log.write(json.dumps({"header": True, "smoothness_weight": args.smoothness_weight,
-                              "edge_alpha": args.edge_alpha}) + "\n")
+        head = {"header": True, "smoothness_weight": args.smoothness_weight,
+                "edge_alpha": args.edge_alpha}
+        if augment is not None:
+            head["augment"] = augment.as_dict()
+        log.write(json.dumps(head) + "\n")
     reader = None
     if args.kitti:
         from .data_reader import AsyncReader, ReaderOpts
         reader = AsyncReader(ReaderOpts(args.kitti, args.batch, args.height, args.width,
-                                        args.nworkers, seed=args.seed + rank))
+                                        args.nworkers, seed=args.seed + rank, augment=augment))
     nbatches = reader.nbatches if reader is not None else args.steps
     step = 0
     for epoch in range(args.epochs):

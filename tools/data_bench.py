@@ -8,6 +8,12 @@
              stream): us per launch and GB/s of algorithmic traffic (8-bit frames read once,
              float32 batch written once)
 
+  --augment  adds the same two readings with the training augmentation: the reader with an
+             AugmentOpts (reader_pairs_per_s_augment), and of_augment_pairs beside
+             of_preprocess_pairs on the same raw batch, launches of the kernels interleaved
+             round by round (augment_kernel_us: identity records, records drawn from the
+             train command's --augment preset, and the preset with a +-10 degree rotation)
+
 Frames: --frames synthetic 375x1242 BGR images (smooth gradients + texture + noise, so zlib
 ratios are in the range of real street scenes), written with the native PNG encoder; pairs
 cycle over them (the page cache holds the files, as it would for a hot dataset).
@@ -46,6 +52,8 @@ def main():
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--batches", type=int, default=40)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--augment", action="store_true",
+                    help="also measure the reader and the kernel with augmentation")
     args = ap.parse_args()
 
     from optical_flow_amd import _lib
@@ -87,6 +95,22 @@ def main():
         res["reader_pairs_per_s"] = round(args.batches * args.batch / dt, 1)
         res["reader_workers"] = args.workers
         raw_bytes = r.raw_bytes
+    if args.augment:
+        from optical_flow_amd.data_reader import AugmentOpts, sample_augment
+        from optical_flow_amd.train import AUGMENT_PRESET
+        preset = AugmentOpts(**AUGMENT_PRESET)
+        aopts = ReaderOpts(None, args.batch, args.height, args.width, args.workers, seed=1,
+                           nslots=4, pairs=pairs, augment=preset)
+        with AsyncReader(aopts) as r:
+            for _ in range(3):
+                r.get_batch()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.batches):
+                b = r.get_batch()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            res["reader_pairs_per_s_augment"] = round(args.batches * args.batch / dt, 1)
     # ---- preprocess kernel alone, on a raw batch resident in HBM (host hand-out layout) ----
     with AsyncReader(ReaderOpts(None, args.batch, args.height, args.width, args.workers, seed=1,
                                 nslots=1, pairs=pairs), pinned=False) as r2:
@@ -94,18 +118,47 @@ def main():
     dev = torch.from_numpy(raw).cuda()
     out = torch.empty((args.batch, args.height, args.width, 6), device="cuda")
     s = torch.cuda.current_stream()
-    for _ in range(3):
-        call("of_preprocess_pairs", C.c_void_p(dev.data_ptr()), args.batch, args.height,
-             args.width, C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream))
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     reps = 50
-    e0.record(s)
-    for _ in range(reps):
+
+    def preprocess():
         call("of_preprocess_pairs", C.c_void_p(dev.data_ptr()), args.batch, args.height,
              args.width, C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream))
-    e1.record(s)
-    torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) * 1e3 / reps
+
+    def timed(launch, reps=reps):
+        """us per launch over `reps` launches between two events (after a warm-up)."""
+        for _ in range(3):
+            launch()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(s)
+        for _ in range(reps):
+            launch()
+        e1.record(s)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps
+
+    us = timed(preprocess)
+    if args.augment:
+        rot = AugmentOpts(**dict(AUGMENT_PRESET, rotate_deg=10.0))
+        records = {"identity": sample_augment(AugmentOpts(), args.batch, args.height, args.width, 1, 0),
+                   "preset": sample_augment(preset, args.batch, args.height, args.width, 1, 0),
+                   "preset_rot10": sample_augment(rot, args.batch, args.height, args.width, 1, 0)}
+        launches = {"preprocess": preprocess}
+        keep = []
+        for name, rec in records.items():
+            prm = torch.from_numpy(rec.view(np.uint8)).cuda()
+            keep.append(prm)
+            launches[name] = (lambda p=prm: call(
+                "of_augment_pairs", C.c_void_p(dev.data_ptr()), args.batch, args.height,
+                args.width, C.c_void_p(p.data_ptr()), C.c_void_p(out.data_ptr()),
+                C.c_void_p(s.cuda_stream)))
+        rounds = {name: [] for name in launches}
+        for _ in range(5):                          # interleaved: drift hits every form alike
+            for name, launch in launches.items():
+                rounds[name].append(timed(launch, 200))
+        res["augment_kernel_us"] = {name: round(float(np.median(v)), 2)
+                                    for name, v in rounds.items()}
+        res["augment_kernel_us_rounds"] = {name: [round(x, 2) for x in v]
+                                           for name, v in rounds.items()}
     alg = 2 * args.batch * 375 * 1242 * 3 + out.numel() * 4
     res["kernel_us"] = round(us, 2)
     res["kernel_alg_bytes"] = alg
