@@ -9,7 +9,14 @@
  * Conventions
  *   - Activations are NHWC; "ld" arguments are pixel strides in elements (>= channels),
  *     so producers can write straight into a channel slice of a wider buffer (virtual
- *     concat, model.py:100-102).
+ *     concat, model.py:100-102).  The conv entry points' GEMM A sources (x, dy, t) need a
+ *     16-byte aligned pointer and ld % 4 == 0 (OF_EINVAL otherwise); every other conv tensor
+ *     (y, z, residual, dx, act_src, add, bn_res) takes any ld >= its channel count and any
+ *     4-byte aligned pointer unless its entry point says otherwise (an unaligned one selects
+ *     the per-element epilogue, the same values; the 7x7 stem forward then runs on the
+ *     implicit GEMM, equal within fp32 summation order).  Memory between rows is the caller's: elements
+ *     [C, ld) of an output row are never written, and elements of an input row beyond the
+ *     channels the entry point says it reads never influence a result (they may hold NaN).
  *   - Kernels are HWIO (Keras layout).  Conv weights are re-packed once per step by
  *     of_conv_pack_weights() into the GEMM-ready layouts the conv kernels read.
  *   - Every launch is stream-ordered on `stream` (a hipStream_t passed as void*); no entry
@@ -97,7 +104,9 @@ int of_conv2d_fwd(const of_conv_desc* d, const float* x, int ldx, const float* w
  * dx[.., ci] = sum_{tap,co} dy * w, for ci < cin_p, then (fused) multiplied by the
  * activation derivative of act_src (the forward output that fed this conv) when
  * act_src != NULL: relu' = [s>0], leaky' = s>0 ? 1 : alpha.
- * dy: [n][ho][wo] pixels of lddy elements, round_up(cout,4) channels read (pad must be 0). */
+ * dy: [n][ho][wo] pixels of lddy elements, round_up(cout,4) channels read (pad must be 0).
+ * The Cout <= 4 layers (of_conv_path(d) == 1) store dx and read act_src as float4 rows: for
+ * them lddx % 4 == 0, ld_act % 4 == 0 and 16-byte aligned dx / act_src, OF_EINVAL otherwise. */
 size_t of_conv2d_dgrad_workspace(const of_conv_desc* d);
 int of_conv2d_dgrad(const of_conv_desc* d, const float* dy, int lddy, const float* w_bwd,
                     const float* act_src, int ld_act, int act, float alpha,
@@ -495,7 +504,9 @@ int of_to_bf16_image(const float* x, int64_t npix, int c, int ldx, void* y16, in
  * (bf16 image, RNE).  col_part
  * (dgrad, optional): per output tile the column sums of the fp32 result, [tiles][N] with tiles =
  * of_conv2d_b16i_tiles(1, d) -- the bias gradient of the layer that produced dy, reduced by
- * of_col_part_reduce.  No workspace (one K slice). */
+ * of_col_part_reduce.  No workspace (one K slice).  Every stride of of_b16i_io is a multiple
+ * of 4 (lda16 of 32) and >= its channel count, fp32 pointers 16-byte and bf16 pointers 8-byte
+ * aligned (OF_EINVAL otherwise). */
 typedef struct of_b16i_io {
   const void* a16; int lda16;
   float* y; int ldy;
@@ -663,8 +674,9 @@ int of_conv2d_dgrad_add_act(const of_conv_desc* d, int precision, const float* d
  * act_src fused into its epilogue (round 5): besides dx = t, per channel sum t and sum t zhat
  * with zhat = (act_src - bn_res - bn_beta) / bn_gamma (bn_res: the residual added before the
  * activation, or NULL) into part ([*nblk][2][cin] floats, of_conv2d_dgrad_bnp_bytes(d)
- * bytes), for of_bn_bwd_final.  The fp32 split 3x3 input gradient with one K slice only:
- * OF_EUNSUPPORTED (nothing launched) otherwise. */
+ * bytes), for of_bn_bwd_final.  The fp32 split 3x3 input gradient with one K slice only, and
+ * on its 16-byte epilogue only (dx, add, act_src and bn_res with ld % 4 == 0 and 16-byte
+ * aligned pointers): OF_EUNSUPPORTED (nothing launched, nothing written) otherwise. */
 size_t of_conv2d_dgrad_bnp_bytes(const of_conv_desc* d);
 int of_conv2d_dgrad_add_act_bnp(const of_conv_desc* d, int precision, const float* dy, int lddy,
                                 const void* w_bwd, const float* add, int ld_add,
@@ -701,7 +713,9 @@ int of_maxpool_bn_relu_bwd(int n, int h, int w, int c, const float* dyp, const f
 /* The stem forward (conv1 + layer1_bn + ReLU, model.py:12-15) with the following MaxPool2D
  * (model.py:17) in its epilogue: y as of_conv2d_fwd_x3 / _bf16 (precision 2 / 1) writes it, and
  * pool (n, ho/2, wo/2, cout) = the 2x2 / stride-2 max of y, bit-identical to of_maxpool2_fwd.
- * OF_EUNSUPPORTED unless the stem kernel takes the layer with an even output. */
+ * OF_EUNSUPPORTED unless the stem kernel takes the layer with an even output; it stores float4
+ * columns, so y and z need ld % 4 == 0 and 16-byte aligned pointers (else OF_EUNSUPPORTED,
+ * nothing written). */
 int of_conv2d_fwd_pool(const of_conv_desc* d, int precision, const float* x, int ldx,
                        const void* w_fwd, const float* bias, const float* bn_gamma,
                        const float* bn_beta, const float* bn_mean, const float* bn_var,

@@ -5929,6 +5929,8 @@ static int conv_wgrad_impl(int prec, const of_conv_desc* d, const float* x, int 
   OF_CHECK_ARG(x && dy && dw && workspace, "conv wgrad: NULL pointer");
   OF_CHECK_ARG(ldx >= d->cin_p && ldx % 4 == 0, "conv wgrad: ldx");
   OF_CHECK_ARG(lddy >= g.cout_p && lddy % 4 == 0, "conv wgrad: lddy");
+  OF_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0,
+               "conv wgrad: x / dy must be 16-byte aligned");
   if (narrow_ok(d)) {
     OF_CHECK_ARG(!bn_g, "conv wgrad: the Cout <= 4 kernels take no BN scale");
     OF_CHECK_ARG(ws_bytes >= narrow_wgrad_ws(d), "conv wgrad: workspace too small");

@@ -77,6 +77,79 @@ def test_pack_table_host_side(lib):
     assert total == e0 + e1
 
 
+def _host(nfloats):
+    """(keep-alive, 16-byte aligned address) of a host float buffer."""
+    raw = (C.c_float * (nfloats + 8))()
+    base = C.addressof(raw)
+    return raw, base + (-base) % 16
+
+
+# The conv entry points' stride and alignment contract (include/oflow.h): each bad argument
+# is refused with OF_EINVAL and a message naming it before anything touches the device.  The
+# pointers are fully sized host buffers; d: 1 x 8 x 8, 14 -> 16 input channels, 30 outputs
+# (round_up(cout, 4) = 32), 3 x 3 stride 1.
+_FWD_OK = dict(ldx=16, ldr=30, ldz=30, ldy=30, x_off=0, res=True, z=True)
+_DG_OK = dict(lddy=32, ld_act=16, lddx=16, dy_off=0, dx_off=0)
+_WG_OK = dict(ldx=16, lddy=32, x_off=0, dy_off=0)
+
+
+@pytest.mark.parametrize("entry,bad,names", [
+    ("fwd", dict(ldx=12), b"ldx"),                      # ldx < cin_p
+    ("fwd", dict(ldx=18), b"ldx"),                      # ldx % 4 != 0
+    ("fwd", dict(ldy=29), b"ldy"),                      # ldy < cout
+    ("fwd", dict(ldr=29), b"ldr"),                      # ldr < cout with a residual
+    ("fwd", dict(ldz=29), b"ldz"),                      # ldz < cout with z
+    ("fwd", dict(x_off=4), b"x "),                      # x not 16-byte aligned
+    ("dgrad", dict(lddy=28), b"lddy"),                  # lddy < round_up(cout, 4)
+    ("dgrad", dict(lddy=34), b"lddy"),                  # lddy % 4 != 0
+    ("dgrad", dict(lddx=15), b"lddx"),                  # lddx < cin_p
+    ("dgrad", dict(ld_act=15), b"ld_act"),              # ld_act < cin_p
+    ("dgrad", dict(dy_off=8), b"dy "),                  # dy not 16-byte aligned
+    ("dgrad_add", dict(ld_add=15), b"ld_add"),          # ld_add < cin_p
+    ("dgrad_add", dict(lddx=12), b"lddx"),
+    ("wgrad", dict(ldx=12), b"ldx"),
+    ("wgrad", dict(ldx=18), b"ldx"),
+    ("wgrad", dict(lddy=28), b"lddy"),
+    ("wgrad", dict(lddy=34), b"lddy"),
+    ("wgrad", dict(x_off=4), b"x "),
+    ("wgrad", dict(dy_off=12), b"dy "),
+    # the Cout <= 4 layers' input gradient stores float4 rows: lddx % 4, ld_act % 4, aligned dx
+    ("dgrad", dict(cout=2, lddy=4, lddx=17), b"dx"),
+    ("dgrad", dict(cout=2, lddy=4, ld_act=18), b"act_src"),
+    ("dgrad", dict(cout=2, lddy=4, dx_off=4), b"dx"),
+], ids=lambda v: None if isinstance(v, bytes) else
+    v if isinstance(v, str) else ",".join("%s=%s" % kv for kv in v.items()))
+def test_conv_stride_contract(lib, entry, bad, names):
+    from optical_flow_amd._lib import ConvDesc, OF_EINVAL
+    cout = bad.get("cout", 30)
+    d = ConvDesc(1, 8, 8, 14, 16, cout, 3, 3, 1, 1, 1, 8, 8)
+    assert lib.of_conv_path(C.byref(d)) == (1 if cout <= 4 else 0)
+    keep, big = _host(64 * 64 + 64)                     # 64 pixels of up to 64 floats, + offsets
+    bufs = [_host(64 * 64 + 64) for _ in range(4)]
+    wk, w = _host(9 * 16 * 32 * 4)
+    wsk, ws = _host(1 << 20)
+    if entry == "fwd":
+        a = dict(_FWD_OK, **bad)
+        st = lib.of_conv2d_fwd(C.byref(d), big + a["x_off"], a["ldx"], w, None, None, None, None,
+                               None, 1e-3, bufs[0][1], a["ldr"], 0, 0.0, bufs[1][1], a["ldz"],
+                               bufs[2][1], a["ldy"], None, 0, None)
+    elif entry == "dgrad":
+        a = dict(_DG_OK, **bad)
+        st = lib.of_conv2d_dgrad(C.byref(d), big + a["dy_off"], a["lddy"], w, bufs[0][1],
+                                 a["ld_act"], 1, 0.0, bufs[1][1] + a["dx_off"], a["lddx"], None, 0,
+                                 None)
+    elif entry == "dgrad_add":
+        a = dict(dict(lddy=32, ld_add=16, lddx=16), **bad)
+        st = lib.of_conv2d_dgrad_add(C.byref(d), big, a["lddy"], w, bufs[0][1], a["ld_add"],
+                                     bufs[1][1], a["lddx"], None, 0, None)
+    else:
+        a = dict(_WG_OK, **bad)
+        st = lib.of_conv2d_wgrad(C.byref(d), big + a["x_off"], a["ldx"], bufs[0][1] + a["dy_off"],
+                                 a["lddy"], bufs[1][1], bufs[2][1], 0, ws, 1 << 22, None)
+    assert st == OF_EINVAL, (st, lib.of_last_error())
+    assert names in lib.of_last_error(), lib.of_last_error()
+
+
 def test_photo_partials(lib):
     assert lib.of_photo_l1_partials(8, 192, 256) == (8 * 192 * 256 + 1023) // 1024
 
