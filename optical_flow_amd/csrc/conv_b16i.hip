@@ -656,19 +656,8 @@ __device__ __forceinline__ int wb_sw(int px, int row_chunks) {
   return row_chunks >= 16 ? (px & 3) << 2 : row_chunks == 8 ? ((px >> 1) & 1) << 2 : 0;
 }
 
-typedef short v4i16 __attribute__((ext_vector_type(4)));
-
-// 8 bf16 (two transposing reads of 4 pixel rows each) of one MFMA operand fragment
-__device__ __forceinline__ bf16x8 tr_frag(const char* base, int off0, int off1) {
-  const v4i16 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) v4i16*)(base + off0));
-  const v4i16 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) v4i16*)(base + off1));
-  typedef short v8i16 __attribute__((ext_vector_type(8)));
-  const v8i16 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
+// (the MFMA operand fragments come from tr_frag, conv_dev.h: two transposing reads of 4 pixel
+// rows each)
 template <int WAVES_CI, int WAVES_CO>
 __global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO, 1) void conv_wgrad_b16i(GemmArgs a) {
   constexpr int NW = WAVES_CI * WAVES_CO, NT = 64 * NW;

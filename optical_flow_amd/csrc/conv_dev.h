@@ -445,6 +445,20 @@ __device__ __forceinline__ uint4 ds_read16(uint32_t addr) {
   return make_uint4(r[0], r[1], r[2], r[3]);
 }
 
+// 8 bf16 of one MFMA operand fragment by two transposing reads (ds_read_b64_tr_b16: a 16-lane
+// group reads 4 rows x 16 columns of bf16, lane 4 q + p gives the address of row q, columns
+// 4 p .. 4 p + 3, lane i receives column i's 4 rows).  Addresses 8-byte aligned, EXEC all ones.
+typedef short v4i16 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ bf16x8 tr_frag(const char* base, int off0, int off1) {
+  const v4i16 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) v4i16*)(base + off0));
+  const v4i16 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) v4i16*)(base + off1));
+  typedef short v8i16 __attribute__((ext_vector_type(8)));
+  const v8i16 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(bf16x8, v);
+}
+
 // 4 fp32 -> 4 bf16 (RNE, v_cvt_pk_bf16_f32), element 0 in the low half of .x
 __device__ __forceinline__ uint2 pack_bf16x4(const float4& v) {
   typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));

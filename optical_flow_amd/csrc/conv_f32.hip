@@ -3411,31 +3411,59 @@ __global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1) void conv_wg
 // to 9 taps x MI row blocks x 6 products: with MI = 2 a loaded and split dy value serves 108
 // MFMAs and no other wave loads it (the 3-tap form: 18, three waves splitting the same value).
 // Workgroup = WAVES_CI x WAVES_CO waves over CIB = 16 MI WAVES_CI input x COB = 16 NJ WAVES_CO
-// output channels; the x halo ((XH + 2) rows x 18 px) is staged once
-// per XH x 16 tile as three split planes x three pixel-shifted copies, single-buffered and
-// register-staged one tile ahead.  LDS row block (plane, s, hy): 8-channel groups of
-// 256 bytes, (ci, octet) in slot (2 (ci & 7) + octet) ^ 2 ((ci >> 3) & 3): the 16x16x32
-// A-fragment reads (16 consecutive channels x 2 octets x 2 rows) and the staging stores (8
-// lanes = 8 channel quads) are both conflict-free.  Output: the split-K slabs (+ bias row).
+// output channels; the x halo ((XH + 2) rows x 18 px) is staged once per XH x 16 tile, every
+// value loaded and split once (split3x4 of four channels of a pixel, as the forward's halo),
+// into one pixel-major image [plane][halo row][halo px][CIB channels] bf16.  The A operand
+// wants 8 consecutive pixels of one channel per lane, so a fragment of tap (r, s) is two
+// transposing reads per plane (tr_frag: a 16-lane group takes 4 pixels x 16 channels, the
+// lane receives its channel's 4 pixels); the tap's column shift s is a pixel-row offset of
+// that image.  The 32-byte channel blocks of a pixel are swizzled by the halo column
+// (wgx3b_sw) so that the two groups of a 32-lane half, 8 pixels apart, and on 128-byte pixel
+// rows the pixels 2 apart of one group, fall on different banks: reads conflict-free.  Two
+// images (69 KB for CIB 32 x XH 8, 83 KB for CIB 64 x XH 4): tile t + 1's float4s are loaded
+// at the top of tile t and split into the other image between its k-steps, one barrier per
+// tile.  Output: the split-K slabs (+ bias row).
+// STG = 0 (the _c3 kernels, of_set_tuning key 40 = 0) is the earlier staging, kept for A/B
+// and as the bitwise reference: three pixel-shifted copies of the halo (a shift is no address
+// offset on a channel-major image), each loaded and split on its own, 92 KB single-buffered,
+// stored between two barriers at the end of the tile.  LDS row block (plane, s, hy):
+// 8-channel groups of 256 bytes, (ci, octet) in slot (2 (ci & 7) + octet) ^ 2 ((ci >> 3) & 3):
+// the 16x16x32 A-fragment reads (16 consecutive channels x 2 octets x 2 rows) and the staging
+// stores (8 lanes = 8 channel quads) are both conflict-free.
 __device__ __forceinline__ int wgx3b_slot(int ci, int oct) {
   return (ci >> 3) * 16 + ((2 * (ci & 7) + oct) ^ (((ci >> 3) & 3) << 1));
 }
 
 // The body is shared with the bf16 weight gradient (NP = 1: x and dy rounded to bf16 RNE, one
 // plane, one MFMA per fragment pair); NP = 3 is the fp32 split.
-template <int WAVES_CI, int WAVES_CO, int XH, int MI, int NP>
+// Swizzle of the pixel-major image's 32-byte channel blocks by the halo column hx: bit 3 of hx
+// moves the two 16-lane groups of a half (pixels 8 apart) to different blocks; on 128-byte
+// pixel rows (CIB = 64) bit 1 of hx moves the rows 2 apart of one group (256 bytes) as well.
+template <int CIB>
+__device__ __forceinline__ int wgx3b_sw(int hx) {
+  return ((hx >> 3) & 1) | (CIB == 64 ? ((hx >> 1) & 1) << 1 : 0);
+}
+
+template <int WAVES_CI, int WAVES_CO, int XH, int MI, int NP, int STG>
 __device__ __forceinline__ void wgrad_x3b_body(const GemmArgs& a) {
   constexpr int NJ = 2 / MI;
   static_assert(MI * NJ == 2, "18 accumulator tiles per wave");
   static_assert(NP == 1 || NP == 3, "planes");
+  static_assert(STG == 0 || STG == 1, "staging: three shifted copies / one pixel-major image");
   constexpr int NT = 64 * WAVES_CI * WAVES_CO;
   constexpr int CIB = 16 * MI * WAVES_CI, COB = 16 * NJ * WAVES_CO, KS = 3, HH = XH + KS - 1;
-  static_assert(XH % 2 == 0 && CIB % 32 == 0, "k-steps of 2 tile rows; 8-channel slot groups");
-  constexpr int XQ = HH * KS * 2 * (CIB / 4), XS = (XQ + NT - 1) / NT;   // (hy, s, half, ci quad)
+  static_assert(XH % 2 == 0 && (CIB == 32 || CIB == 64), "k-steps of 2 tile rows; wgx3b_sw");
+  // STG 0: slots (hy, s, half, ci quad) of 8 pixels; STG 1: slots (hy, hx, ci quad) of 1 pixel
+  constexpr int HW = TT_W + KS - 1;
+  constexpr int XQ = STG ? HH * HW * (CIB / 4) : HH * KS * 2 * (CIB / 4), XS = (XQ + NT - 1) / NT;
   constexpr int RB = CIB * 2;                      // uint4 per (plane, s, hy) row block
   constexpr int PL = KS * HH * RB;                 // uint4 per plane
-  static_assert(NT / 64 * 512 * 4 <= NP * PL * 16, "epilogue images fit LDS");
-  __shared__ uint4 Xs[NP * PL];
+  constexpr int PXB = CIB * 2;                     // STG 1: bytes per halo pixel and plane
+  constexpr int PLB = HH * HW * PXB, IMGB = NP * PLB;   // bytes per plane, per image
+  constexpr int LDSB = STG ? 2 * IMGB : NP * PL * 16;
+  static_assert(NT / 64 * 512 * 4 <= LDSB && LDSB % 16 == 0, "epilogue images fit LDS");
+  __shared__ uint4 Xs[LDSB / 16];
+  char* const xlds = reinterpret_cast<char*>(Xs);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -3459,7 +3487,8 @@ __device__ __forceinline__ void wgrad_x3b_body(const GemmArgs& a) {
   // ---- x halo slots (channel quad fastest: coalesced 16-byte lanes of one pixel)
   const int xcq = tid % (CIB / 4);
   const bool xc_ok = ci0 + 4 * xcq < a.kc;
-  float4 xv[XS][8];
+  constexpr int XE = STG ? 1 : 8;                  // pixels per slot
+  float4 xv[XS][XE];
   auto load_x = [&](int t) {
     const int b = t / (tiles_x * tiles_y);
     const int trem = t - b * tiles_x * tiles_y;
@@ -3468,24 +3497,49 @@ __device__ __forceinline__ void wgrad_x3b_body(const GemmArgs& a) {
 #pragma unroll
     for (int j = 0; j < XS; ++j) {
       const int q = tid + NT * j;
-      const int r2 = q / (CIB / 4);
-      const int half = r2 & 1, s = (r2 >> 1) % KS, hy = (r2 >> 1) / KS;
-      const int iy = iy0 + hy;
-      const bool rok = q < XQ && xc_ok && (unsigned)iy < (unsigned)a.h;
-      const int ix0 = ix00 + 8 * half + s;
-      const int base = ((b * a.h + iy) * a.w + ix0) * a.lda + ci0 + 4 * xcq;
+      if constexpr (STG == 1) {
+        const int hp = q / (CIB / 4);
+        const int hy = hp / HW, hx = hp - hy * HW;
+        const int iy = iy0 + hy, ix = ix00 + hx;
+        const bool ok = q < XQ && xc_ok && (unsigned)iy < (unsigned)a.h &&
+                        (unsigned)ix < (unsigned)a.w;
+        const int base = ((b * a.h + iy) * a.w + ix) * a.lda + ci0 + 4 * xcq;
+        xv[j][0] = bload4(rx, ok ? (uint32_t)(base * 4) : kOOB);
+      } else {
+        const int r2 = q / (CIB / 4);
+        const int half = r2 & 1, s = (r2 >> 1) % KS, hy = (r2 >> 1) / KS;
+        const int iy = iy0 + hy;
+        const bool rok = q < XQ && xc_ok && (unsigned)iy < (unsigned)a.h;
+        const int ix0 = ix00 + 8 * half + s;
+        const int base = ((b * a.h + iy) * a.w + ix0) * a.lda + ci0 + 4 * xcq;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const bool ok = rok && (unsigned)(ix0 + e) < (unsigned)a.w;
-        xv[j][e] = bload4(rx, ok ? (uint32_t)((base + e * a.lda) * 4) : kOOB);
+        for (int e = 0; e < 8; ++e) {
+          const bool ok = rok && (unsigned)(ix0 + e) < (unsigned)a.w;
+          xv[j][e] = bload4(rx, ok ? (uint32_t)((base + e * a.lda) * 4) : kOOB);
+        }
       }
     }
   };
-  auto store_x = [&]() {
-#pragma unroll
-    for (int j = 0; j < XS; ++j) {
-      const int q = tid + NT * j;
-      if (XQ % NT == 0 || q < XQ) {
+  // STG 0: every slot into the one halo; STG 1: slot j into image `buf` (4 channels of one
+  // pixel: 8 bytes per plane, as the forward's halo)
+  auto store_x = [&](int j, int buf) {
+    const int q = tid + NT * j;
+    if (XQ % NT == 0 || q < XQ) {
+      if constexpr (STG == 1) {
+        const int hp = q / (CIB / 4);
+        const int hx = hp % HW;
+        char* dst = xlds + buf * IMGB + hp * PXB + (((xcq >> 2) ^ wgx3b_sw<CIB>(hx)) << 5) +
+                    8 * (xcq & 3);
+        if constexpr (NP == 1) {
+          *reinterpret_cast<uint2*>(dst) = pack_bf16x4(xv[j][0]);
+        } else {
+          uint2 h, m, l;
+          split3x4(xv[j][0], h, m, l);
+          *reinterpret_cast<uint2*>(dst) = h;
+          *reinterpret_cast<uint2*>(dst + PLB) = m;
+          *reinterpret_cast<uint2*>(dst + 2 * PLB) = l;
+        }
+      } else {
         const int r2 = q / (CIB / 4);
         const int half = r2 & 1, s = (r2 >> 1) % KS, hy = (r2 >> 1) / KS;
         uint4* blk = &Xs[(s * HH + hy) * RB];
@@ -3508,6 +3562,10 @@ __device__ __forceinline__ void wgrad_x3b_body(const GemmArgs& a) {
         }
       }
     }
+  };
+  auto store_x_all = [&](int buf) {
+#pragma unroll
+    for (int j = 0; j < XS; ++j) store_x(j, buf);
   };
   // ---- dy fragments: column blocks j < NJ (co = co0 + wco0 + 16 j + l16), pixels
   // 8 (lq & 1) .. + 7 of tile row 2 kk + (lq >> 1)
@@ -3564,6 +3622,24 @@ __device__ __forceinline__ void wgrad_x3b_body(const GemmArgs& a) {
   int a_lane[MI];
 #pragma unroll
   for (int i = 0; i < MI; ++i) a_lane[i] = prow * RB + wgx3b_slot(wci0 + 16 * i + l16, lq & 1);
+  // STG 1: the same fragment by two transposing reads per plane.  The lane's 16-lane group lq
+  // reads the pixels pcol + s + 4 h .. + 3 (h = 0, 1) of halo row 2 kk + prow + r x the row
+  // block's 16 channels; lane 4 q + p of the group gives the address of pixel q, channels
+  // 4 p .. 4 p + 3 and lane l16 receives its channel's four pixels.  Byte offsets per (s, h, i)
+  // (the swizzle depends on the pixel); the halo row and the plane are immediate offsets.
+  int a_tr[KS][2][MI];
+  if constexpr (STG == 1) {
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+          const int hx = pcol + s + 4 * h + ((lane >> 2) & 3);
+          a_tr[s][h][i] = (prow * HW + hx) * PXB +
+                          ((((wci0 >> 4) + i) ^ wgx3b_sw<CIB>(hx)) << 5) + 8 * (lane & 3);
+        }
+  }
   const bool do_colsum = a.colsum && tile_ci == 0 && wci0 == 0;
   float colacc[NJ];
 #pragma unroll
@@ -3573,13 +3649,24 @@ __device__ __forceinline__ void wgrad_x3b_body(const GemmArgs& a) {
   if (steps > 0) {
     load_x(t_begin);
     load_dy(dcur, t_begin, 0);
-    store_x();
+    store_x_all(0);
   }
   __syncthreads();
   for (int i = 0; i < steps; ++i) {
     const int t = t_begin + i;
     const bool more = i + 1 < steps;
     if (more) load_x(t + 1);
+    // STG 1: tile i is read from image i & 1 while tile i + 1 goes into the other one
+    const int buf = STG ? i & 1 : 0;
+    int a_cur[KS][2][MI];
+    if constexpr (STG == 1) {
+#pragma unroll
+      for (int s = 0; s < KS; ++s)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int ii = 0; ii < MI; ++ii) a_cur[s][h][ii] = a_tr[s][h][ii] + buf * IMGB;
+    }
 #pragma unroll
     for (int kk = 0; kk < XH / 2; ++kk) {
       if (kk + 1 < XH / 2) load_dy(dnext, t, kk + 1);
@@ -3606,9 +3693,17 @@ __device__ __forceinline__ void wgrad_x3b_body(const GemmArgs& a) {
         const int r = tap / KS, s = tap % KS;
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
-          const int xa = (s * HH + 2 * kk + r) * RB + a_lane[i];
+          if constexpr (STG == 1) {
 #pragma unroll
-          for (int p = 0; p < NP; ++p) f[i][p] = __builtin_bit_cast(bf16x8, Xs[p * PL + xa]);
+            for (int p = 0; p < NP; ++p) {
+              const int ro = p * PLB + (2 * kk + r) * HW * PXB;
+              f[i][p] = tr_frag(xlds, a_cur[s][0][i] + ro, a_cur[s][1][i] + ro);
+            }
+          } else {
+            const int xa = (s * HH + 2 * kk + r) * RB + a_lane[i];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) f[i][p] = __builtin_bit_cast(bf16x8, Xs[p * PL + xa]);
+          }
         }
       };
       load_a(fa[0], 0);
@@ -3644,10 +3739,22 @@ __device__ __forceinline__ void wgrad_x3b_body(const GemmArgs& a) {
       for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int e = 0; e < 8; ++e) dcur[j][e] = dnext[j][e];
+      if constexpr (STG == 1) {
+        // the next tile's slots, spread over the k-steps: the split runs beside the SIMD's
+        // other wave's MFMAs, and nobody reads that image before the barrier below
+        if (more) {
+#pragma unroll
+          for (int j = 0; j < XS; ++j)
+            if (j * (XH / 2) / XS == kk) store_x(j, buf ^ 1);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
     __syncthreads();              // every wave is done with this tile's halo
-    if (more) store_x();
-    __syncthreads();
+    if constexpr (STG == 0) {
+      if (more) store_x_all(0);
+      __syncthreads();
+    }
   }
 
   // ---- raw partial sums into this K slice's slab (+ bias column sums in row M)
@@ -3706,13 +3813,24 @@ __device__ __forceinline__ void wgrad_x3b_body(const GemmArgs& a) {
 
 template <int WAVES_CI, int WAVES_CO, int XH, int MI = 1>
 __global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO, 1) void conv_wgrad_tile_x3b(GemmArgs a) {
-  wgrad_x3b_body<WAVES_CI, WAVES_CO, XH, MI, 3>(a);
+  wgrad_x3b_body<WAVES_CI, WAVES_CO, XH, MI, 3, 1>(a);
 }
 
 // bf16 (configs 3-5) 3x3 stride-1 weight gradient on the 9-tap structure, one plane.
 template <int WAVES_CI, int WAVES_CO, int XH>
 __global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO, 1) void conv_wgrad_tile_b16(GemmArgs a) {
-  wgrad_x3b_body<WAVES_CI, WAVES_CO, XH, 1, 1>(a);
+  wgrad_x3b_body<WAVES_CI, WAVES_CO, XH, 1, 1, 1>(a);
+}
+
+// The same two on the three shifted halo copies (of_set_tuning key 40 = 0): bitwise the same
+// sums, kept for A/B measurements and as the reference of the staging test.
+template <int WAVES_CI, int WAVES_CO, int XH, int MI = 1>
+__global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO, 1) void conv_wgrad_tile_x3b_c3(GemmArgs a) {
+  wgrad_x3b_body<WAVES_CI, WAVES_CO, XH, MI, 3, 0>(a);
+}
+template <int WAVES_CI, int WAVES_CO, int XH>
+__global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO, 1) void conv_wgrad_tile_b16_c3(GemmArgs a) {
+  wgrad_x3b_body<WAVES_CI, WAVES_CO, XH, 1, 1, 0>(a);
 }
 
 // ---- fp32 weight gradient on the split-bf16 MFMA: implicit GEMM (other shapes) ------------
@@ -4829,6 +4947,10 @@ static int g_wgx3b = 1;
 // MI = 2 halves the dy loads and splits per MFMA and measured the same (dec3.c1 0.516 vs
 // 0.517 ms): the split VALU is not what bounds the kernel.
 static int g_wgx3b_mi = 1;
+// of_set_tuning key 40: the 9-tap weight gradients' x halo (conv_wgrad_tile_x3b / _b16) as one
+// pixel-major image read with transposing LDS reads, double-buffered (1, default), or as
+// three pixel-shifted copies, single-buffered (0: the _c3 kernels; bitwise the same sums).
+static int g_wgx3b_stage = 1;
 // of_set_tuning key 33: at least this many K tiles per split-K slice of the 9-tap weight
 // gradients (conv_wgrad_tile_x3b / _b16).  Every slice writes a 9 x cin x cout fp32 slab that
 // wgrad_reduce_kernel reads back: with one slice per CU the slabs are a fixed ~38 MB per launch
@@ -5471,6 +5593,7 @@ int of_set_tuning(int key, int value) {
   if (key == 37 && value >= 0 && value <= 16) { g_det_fx_grid = value; return OF_OK; }
   if (key == 38 && value >= 0 && value <= 131072) { g_det_lds_probe = value; return OF_OK; }
   if (key == 39 && (value == 0 || value == 1)) { g_abl_noact = value; return OF_OK; }
+  if (key == 40 && (value == 0 || value == 1)) { g_wgx3b_stage = value; return OF_OK; }
   return fail(OF_EINVAL, "of_set_tuning: unknown key/value " + std::to_string(key));
 }
 
@@ -5985,7 +6108,13 @@ static int conv_wgrad_impl(int prec, const of_conv_desc* d, const float* x, int 
     a.tiles_total = (int)cdiv(g.cin_p, cib) * a.n_tiles;
     dim3 grid(a.tiles_total * a.splits);
     if (timing_on()) timing_begin(s);
-    if (cfg == 4) hipLaunchKernelGGL((conv_wgrad_tile_b16<2, 2, 8>), grid, dim3(256), 0, s, a);
+    if (g_wgx3b_stage == 0) {   // three shifted halo copies
+      if (cfg == 4) hipLaunchKernelGGL((conv_wgrad_tile_b16_c3<2, 2, 8>), grid, dim3(256), 0, s, a);
+      else if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_b16_c3<2, 4, 8>), grid, dim3(512), 0, s, a);
+      else if (cfg == 1) hipLaunchKernelGGL((conv_wgrad_tile_b16_c3<2, 3, 8>), grid, dim3(384), 0, s, a);
+      else if (cfg == 2) hipLaunchKernelGGL((conv_wgrad_tile_b16_c3<4, 2, 4>), grid, dim3(512), 0, s, a);
+      else hipLaunchKernelGGL((conv_wgrad_tile_b16_c3<4, 1, 4>), grid, dim3(256), 0, s, a);
+    } else if (cfg == 4) hipLaunchKernelGGL((conv_wgrad_tile_b16<2, 2, 8>), grid, dim3(256), 0, s, a);
     else if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_b16<2, 4, 8>), grid, dim3(512), 0, s, a);
     else if (cfg == 1) hipLaunchKernelGGL((conv_wgrad_tile_b16<2, 3, 8>), grid, dim3(384), 0, s, a);
     else if (cfg == 2) hipLaunchKernelGGL((conv_wgrad_tile_b16<4, 2, 4>), grid, dim3(512), 0, s, a);
@@ -6003,7 +6132,19 @@ static int conv_wgrad_impl(int prec, const of_conv_desc* d, const float* x, int 
     if (timing_on()) timing_begin(s);
     const bool x3b = g_wgx3b == 2 || (g_wgx3b == 1 && cfg == 0) || cfg == 4;
     if (x3b) {
-      if (g_wgx3b_mi == 2) {   // waves of 32 ci x 16 co
+      if (g_wgx3b_stage == 0 && g_wgx3b_mi == 2) {   // three shifted halo copies
+        if (cfg == 4) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<1, 4, 8, 2>), grid, dim3(256), 0, s, a);
+        else if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<1, 8, 8, 2>), grid, dim3(512), 0, s, a);
+        else if (cfg == 1) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<1, 6, 8, 2>), grid, dim3(384), 0, s, a);
+        else if (cfg == 2) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<2, 4, 4, 2>), grid, dim3(512), 0, s, a);
+        else hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<2, 2, 4, 2>), grid, dim3(256), 0, s, a);
+      } else if (g_wgx3b_stage == 0) {
+        if (cfg == 4) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<2, 2, 8>), grid, dim3(256), 0, s, a);
+        else if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<2, 4, 8>), grid, dim3(512), 0, s, a);
+        else if (cfg == 1) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<2, 3, 8>), grid, dim3(384), 0, s, a);
+        else if (cfg == 2) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<4, 2, 4>), grid, dim3(512), 0, s, a);
+        else hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<4, 1, 4>), grid, dim3(256), 0, s, a);
+      } else if (g_wgx3b_mi == 2) {   // waves of 32 ci x 16 co
         if (cfg == 4) hipLaunchKernelGGL((conv_wgrad_tile_x3b<1, 4, 8, 2>), grid, dim3(256), 0, s, a);
         else if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_x3b<1, 8, 8, 2>), grid, dim3(512), 0, s, a);
         else if (cfg == 1) hipLaunchKernelGGL((conv_wgrad_tile_x3b<1, 6, 8, 2>), grid, dim3(384), 0, s, a);
