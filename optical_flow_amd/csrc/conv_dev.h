@@ -618,6 +618,13 @@ __device__ __forceinline__ void direct_dgrad_f32(const GemmArgs& a, f32x4 (&acc)
 
 // conv_ws.hip: launch conv_tile_ws for a planned bf16 3x3 fwd / dgrad (no timing, no split-K
 // epilogue: the caller's)
-int launch_tile_ws_kernel(const GemmArgs& a, int mode, hipStream_t s);
+// One kernel instance as the host launches it (conv_f32.hip: launch records).
+struct Launch {
+  void (*fn)(GemmArgs);
+  int threads, kind;
+  const char* name;   // for check_launch
+};
+// conv_tile_ws by N tile and mode; kind: the cfg alone
+Launch tile_ws_launch(const GemmArgs& a, int mode);
 
 }  // namespace oflow

@@ -4998,39 +4998,80 @@ int launch_splitk_epilogue(const GemmArgs& a, hipStream_t s) {
   return check_launch("conv_splitk_epilogue");
 }
 
-// Timing kinds: mode * 8 + tile config (0: 128x128, 1: 128x96, 2: 256x64, 3: 256x32) -- one
-// per conv_gemm_f32 template instance.
+// ---- launch records ---------------------------------------------------------------------
+// Timing kinds are base + mode * 8 + cfg, one per kernel instance a call can select; bench.py
+// kind_parts decodes them, so the numbers are a contract with it.  conv_b16i.hip owns 288+.
+constexpr int KIND_F32 = 0, KIND_TILE_F32 = 32, KIND_BF16 = 64, KIND_TILE_BF16 = 96,
+              KIND_TILE_X3 = 128, KIND_GEMM_X3 = 160, KIND_TILE_B16 = 192, KIND_WGRAD_B16 = 216,
+              KIND_TILE_WS = 224, KIND_GEMM_B16 = 240;
+constexpr int KIND_STEM_X3 = 184, KIND_STEM_WG_X3 = 185;     // conv_stem_x3, conv_wgrad_stem_x3
+constexpr int KIND_STEM_B16 = 186, KIND_STEM_WG_B16 = 187;   // their one-plane bf16 forms
+constexpr int KIND_NARROW = 7;                               // cfg slot of the Cout <= 4 VALU path
+constexpr int kind(int base, int mode, int cfg) { return base + mode * 8 + cfg; }
+// conv_wgrad_tile_x3 (3-tap) has cfg 0-3 (144-147); the 9-tap conv_wgrad_tile_x3b follows it
+// with its cfg 0-4 as 148-152 (bench.py X3_WGT 4 + cfg)
+constexpr int KIND_WGRAD_X3B = kind(KIND_TILE_X3, MODE_WGRAD, 4);
+
+// Launch (conv_dev.h): one kernel instance as the host launches it.  Tables hold the kind of
+// cfg 0; with_cfg() adds the index.  threads is written once per family, by the expression of
+// the kernel's __launch_bounds__.
+constexpr Launch with_cfg(Launch l, int cfg) { return {l.fn, l.threads, l.kind + cfg, l.name}; }
+
+// timing_begin -> launch -> timing_end -> check_launch; the forward and input-gradient
+// families then reduce their K slices.  grid 0: one workgroup per tile and K slice.
 template <int MODE>
-int launch_gemm(const GemmArgs& a, hipStream_t s, double flops) {
-  const int bn = pick_bn(a.N);
-  dim3 grid(a.tiles_total * a.splits), block(256);
-  const int cfg = bn == 128 ? 0 : bn == 96 ? 1 : bn == 64 ? 2 : 3;
+int launch(const Launch& l, const GemmArgs& a, hipStream_t s, double flops, unsigned grid = 0) {
   if (timing_on()) timing_begin(s);
-  if (cfg == 0) hipLaunchKernelGGL((conv_gemm_f32<128, 128, 2, 2, MODE>), grid, block, 0, s, a);
-  else if (cfg == 1) hipLaunchKernelGGL((conv_gemm_f32<128, 96, 4, 1, MODE>), grid, block, 0, s, a);
-  else if (cfg == 2) hipLaunchKernelGGL((conv_gemm_f32<256, 64, 4, 1, MODE>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((conv_gemm_f32<256, 32, 4, 1, MODE>), grid, block, 0, s, a);
-  if (timing_on()) timing_end(s, MODE * 8 + cfg, flops);
-  int st = check_launch("conv_gemm_f32");
+  hipLaunchKernelGGL(l.fn, dim3(grid ? grid : a.tiles_total * a.splits), dim3(l.threads), 0, s, a);
+  if (timing_on()) timing_end(s, l.kind, flops);
+  int st = check_launch(l.name);
   if (st || MODE == MODE_WGRAD || a.splits == 1) return st;
   return launch_splitk_epilogue<MODE>(a, s);
 }
+// conv_stem_x3 takes the tile count as a second argument: __launch_bounds__(CO * 8, ...)
+struct StemLaunch {
+  void (*fn)(GemmArgs, int);
+  int threads, kind;
+};
+template <int CO, int NP = 3>
+constexpr StemLaunch stem_rec() {
+  return {conv_stem_x3<CO, NP>, CO * 8, NP == 1 ? KIND_STEM_B16 : KIND_STEM_X3};
+}
 
-// bf16 instances: timing kinds 64 + mode * 8 + tile config.
+// Tile config by N tile: 0: BN 128, 1: 96, 2: 64, 3: 32.
+int bn_cfg(int N) { return N > 96 ? 0 : N > 64 ? 1 : N > 32 ? 2 : 3; }
+
+// conv_gemm_f32 / conv_gemm_bf16 / conv_wgrad_bf16: __launch_bounds__(256, 2)
+template <int BM, int BN, int WM, int WN, int MODE>
+constexpr Launch gemm_f32_rec() {
+  return {conv_gemm_f32<BM, BN, WM, WN, MODE>, 256, kind(KIND_F32, MODE, 0), "conv_gemm_f32"};
+}
+template <int BM, int BN, int WM, int WN, int MODE>
+constexpr Launch gemm_bf16_rec() {
+  return {conv_gemm_bf16<BM, BN, WM, WN, MODE>, 256, kind(KIND_BF16, MODE, 0), "conv_gemm_bf16"};
+}
+template <int BM, int BN, int WM, int WN>
+constexpr Launch wgrad_bf16_rec() {
+  return {conv_wgrad_bf16<BM, BN, WM, WN>, 256, kind(KIND_BF16, MODE_WGRAD, 0), "conv_wgrad_bf16"};
+}
+
+// cfg 0: 128 x 128 tiles, 1: 128 x 96, 2: 256 x 64, 3: 256 x 32 (pick_bm / pick_bn)
 template <int MODE>
-int launch_gemm_bf16(const GemmArgs& a, hipStream_t s, double flops) {
-  const int bn = pick_bn(a.N);
-  dim3 grid(a.tiles_total * a.splits), block(256);
-  const int cfg = bn == 128 ? 0 : bn == 96 ? 1 : bn == 64 ? 2 : 3;
-  if (timing_on()) timing_begin(s);
-  if (cfg == 0) hipLaunchKernelGGL((conv_gemm_bf16<128, 128, 2, 2, MODE>), grid, block, 0, s, a);
-  else if (cfg == 1) hipLaunchKernelGGL((conv_gemm_bf16<128, 96, 4, 1, MODE>), grid, block, 0, s, a);
-  else if (cfg == 2) hipLaunchKernelGGL((conv_gemm_bf16<256, 64, 4, 1, MODE>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((conv_gemm_bf16<256, 32, 4, 1, MODE>), grid, block, 0, s, a);
-  if (timing_on()) timing_end(s, 64 + MODE * 8 + cfg, flops);
-  int st = check_launch("conv_gemm_bf16");
-  if (st || a.splits == 1) return st;
-  return launch_splitk_epilogue<MODE>(a, s);
+Launch gemm_f32_launch(const GemmArgs& a) {
+  static const Launch T[4] = {gemm_f32_rec<128, 128, 2, 2, MODE>(), gemm_f32_rec<128, 96, 4, 1, MODE>(),
+                              gemm_f32_rec<256, 64, 4, 1, MODE>(), gemm_f32_rec<256, 32, 4, 1, MODE>()};
+  return with_cfg(T[bn_cfg(a.N)], bn_cfg(a.N));
+}
+template <int MODE>
+Launch gemm_bf16_launch(const GemmArgs& a) {
+  static const Launch T[4] = {gemm_bf16_rec<128, 128, 2, 2, MODE>(), gemm_bf16_rec<128, 96, 4, 1, MODE>(),
+                              gemm_bf16_rec<256, 64, 4, 1, MODE>(), gemm_bf16_rec<256, 32, 4, 1, MODE>()};
+  return with_cfg(T[bn_cfg(a.N)], bn_cfg(a.N));
+}
+Launch wgrad_bf16_launch(const GemmArgs& a) {
+  static const Launch T[4] = {wgrad_bf16_rec<128, 128, 2, 2>(), wgrad_bf16_rec<128, 96, 4, 1>(),
+                              wgrad_bf16_rec<256, 64, 4, 1>(), wgrad_bf16_rec<256, 32, 4, 1>()};
+  return with_cfg(T[bn_cfg(a.N)], bn_cfg(a.N));
 }
 
 // bf16 3x3 stride-1 fwd / dgrad: halo-tiled kernel (conv_tile_bf16).
@@ -5079,6 +5120,25 @@ static int g_x3_bn64 = 0;
 // of_set_tuning key 39: timing ablation -- the split 3x3 input gradients without their act'
 // source reads (RESULTS ARE WRONG: the derivative taken as 1; A/B timing only; default 0)
 static int g_abl_noact = 0;
+// The K split (1 to 8 slices of whole chunks) with the least modelled time, in units of one
+// chunk: rounds of `slots` workgroups x (chunks per slice + 1 for prologue and epilogue), plus
+// `ep` tenths of a chunk per slice and tile round for the slab write and epilogue pass.
+int best_split(int chunks, int64_t tiles, int slots, int ep) {
+  int best = 1;
+  double best_cost = 1e30;
+  for (int sp = 1; sp <= std::min(8, chunks); ++sp) {
+    const int per = (int)cdiv(chunks, sp);
+    if (cdiv(chunks, per) != sp) continue;            // not a distinct slice count
+    const double cost = (double)cdiv(tiles * sp, slots) * (per + 1.0) +
+                        (sp > 1 ? 0.1 * ep * sp * tiles / (double)slots : 0.0);
+    if (cost < best_cost - 1e-9) {
+      best_cost = cost;
+      best = sp;
+    }
+  }
+  return best;
+}
+
 GemmArgs tile_args(const of_conv_desc* d, const Geo& g, int mode, bool x3 = false,
                    bool b16 = false, bool ws = false) {
   GemmArgs a = base_args(d);
@@ -5122,9 +5182,7 @@ GemmArgs tile_args(const of_conv_desc* d, const Geo& g, int mode, bool x3 = fals
   a.splits = 1;
   a.k_per_split = a.K;
   if (x3 || b16 || ws) {
-    // One workgroup per CU (conv_tile_b16: two): choose the K split with the least modelled time, in units of one
-    // chunk (9 taps): rounds of 256 workgroups x (chunks per slice + 1 for prologue and
-    // epilogue), plus 0.5 per slice and tile round for the slab write and epilogue pass.
+    // One workgroup per CU (conv_tile_b16: two): best_split() in chunks of 9 taps.
     // (Measured: enc.l3 384 tiles unsplit, dec1 192 tiles unsplit, enc.l4 96 tiles in 2.)
     // (The single-buffered BN = 128 4 x 32 configuration, used from X3_NB1_MIN tiles, runs
     // two workgroups per CU.)
@@ -5132,20 +5190,7 @@ GemmArgs tile_args(const of_conv_desc* d, const Geo& g, int mode, bool x3 = fals
     const int slots = !ws && ((b16 && !tall) || x3_nb1_candidate(a, tall) || a.bn_tile == 64 ||
                               (g_x3_bn64 && bn64))
                           ? 2 * device_cus() : device_cus();
-    int best = 1;
-    double best_cost = 1e30;
-    for (int sp = 1; sp <= std::min(8, a.K); ++sp) {
-      const int per = (int)cdiv(a.K, sp);
-      if (cdiv(a.K, per) != sp) continue;            // not a distinct slice count
-      const int64_t w = (int64_t)a.tiles_total * sp;
-      const double cost = (double)cdiv(w, slots) * (per + 1.0) +
-                          (sp > 1 ? 0.1 * g_x3t_ep * sp * a.tiles_total / (double)slots : 0.0);
-      if (cost < best_cost - 1e-9) {
-        best_cost = cost;
-        best = sp;
-      }
-    }
-    a.k_per_split = (int)cdiv(a.K, best);
+    a.k_per_split = (int)cdiv(a.K, best_split(a.K, a.tiles_total, slots, g_x3t_ep));
     a.splits = (int)cdiv(a.K, a.k_per_split);
   } else if (a.tiles_total < 2 * device_cus()) {
     int sp = std::max(1, (4 * device_cus()) / a.tiles_total);
@@ -5156,28 +5201,35 @@ GemmArgs tile_args(const of_conv_desc* d, const Geo& g, int mode, bool x3 = fals
   return a;
 }
 
+bool tall_tile(const GemmArgs& a) { return a.bm == X3_TH0 * TF_W; }
+
+// conv_tile_bf16 / conv_tile_x3 / conv_tile_b16: __launch_bounds__(64 * WAVES_M * WAVES_N, ...)
+template <int BN, int WM, int WN, int MODE, int TH = OF_TF_H, int PF = 1>
+constexpr Launch tile_bf16_rec() {
+  return {conv_tile_bf16<BN, WM, WN, MODE, TH, PF>, 64 * WM * WN, kind(KIND_TILE_BF16, MODE, 0),
+          "conv_tile_bf16"};
+}
+template <int BN, int WM, int WN, int MODE, int TH, int NB = 2>
+constexpr Launch tile_x3_rec() {
+  return {conv_tile_x3<BN, WM, WN, MODE, TH, NB>, 64 * WM * WN, kind(KIND_TILE_X3, MODE, 0), "conv_tile_x3"};
+}
+template <int BN, int WM, int WN, int MODE, int TH>
+constexpr Launch tile_b16_rec() {
+  return {conv_tile_b16<BN, WM, WN, MODE, TH>, 64 * WM * WN, kind(KIND_TILE_B16, MODE, 0), "conv_tile_b16"};
+}
+
+// bf16 3x3 stride-1 fwd / dgrad on conv_tile_bf16: cfg 0-3 by N tile on 4 x 32 output tiles,
+// 4: BN 128 on 8 x 32; [PF] is of_set_tuning key 20.
 template <int MODE>
-int launch_tile_bf16(const GemmArgs& a, hipStream_t s, double flops) {
-  const int bn = pick_bn(a.N);
-  dim3 grid(a.tiles_total * a.splits), block(256);
-  const bool tall = a.bm == X3_TH0 * TF_W;
-  const int cfg = bn == 128 ? (tall ? 4 : 0) : bn == 96 ? 1 : bn == 64 ? 2 : 3;
-  if (timing_on()) timing_begin(s);
-  if (!g_tile16_pf) {
-    if (cfg == 4) hipLaunchKernelGGL((conv_tile_bf16<128, 4, 2, MODE, X3_TH0, 0>), grid, dim3(512), 0, s, a);
-    else if (cfg == 0) hipLaunchKernelGGL((conv_tile_bf16<128, 2, 2, MODE, OF_TF_H, 0>), grid, block, 0, s, a);
-    else if (cfg == 1) hipLaunchKernelGGL((conv_tile_bf16<96, 4, 1, MODE, OF_TF_H, 0>), grid, block, 0, s, a);
-    else if (cfg == 2) hipLaunchKernelGGL((conv_tile_bf16<64, 2, 2, MODE, OF_TF_H, 0>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_tile_bf16<32, 4, 1, MODE, OF_TF_H, 0>), grid, block, 0, s, a);
-  } else if (cfg == 4) hipLaunchKernelGGL((conv_tile_bf16<128, 4, 2, MODE, X3_TH0>), grid, dim3(512), 0, s, a);
-  else if (cfg == 0) hipLaunchKernelGGL((conv_tile_bf16<128, 2, 2, MODE>), grid, block, 0, s, a);
-  else if (cfg == 1) hipLaunchKernelGGL((conv_tile_bf16<96, 4, 1, MODE>), grid, block, 0, s, a);
-  else if (cfg == 2) hipLaunchKernelGGL((conv_tile_bf16<64, 2, 2, MODE>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((conv_tile_bf16<32, 4, 1, MODE>), grid, block, 0, s, a);
-  if (timing_on()) timing_end(s, 64 + 32 + MODE * 8 + cfg, flops);
-  int st = check_launch("conv_tile_bf16");
-  if (st || a.splits == 1) return st;
-  return launch_splitk_epilogue<MODE>(a, s);
+Launch tile_bf16_launch(const GemmArgs& a) {
+  static const Launch T[2][5] = {
+      {tile_bf16_rec<128, 2, 2, MODE, OF_TF_H, 0>(), tile_bf16_rec<96, 4, 1, MODE, OF_TF_H, 0>(),
+       tile_bf16_rec<64, 2, 2, MODE, OF_TF_H, 0>(), tile_bf16_rec<32, 4, 1, MODE, OF_TF_H, 0>(),
+       tile_bf16_rec<128, 4, 2, MODE, X3_TH0, 0>()},
+      {tile_bf16_rec<128, 2, 2, MODE>(), tile_bf16_rec<96, 4, 1, MODE>(), tile_bf16_rec<64, 2, 2, MODE>(),
+       tile_bf16_rec<32, 4, 1, MODE>(), tile_bf16_rec<128, 4, 2, MODE, X3_TH0>()}};
+  const int cfg = bn_cfg(a.N) == 0 && tall_tile(a) ? 4 : bn_cfg(a.N);
+  return with_cfg(T[g_tile16_pf != 0][cfg], cfg);
 }
 
 struct WgradPlan {
@@ -5185,70 +5237,43 @@ struct WgradPlan {
   int64_t split_stride;
 };
 
-// fp32 3x3 stride-1 fwd / dgrad on the split-bf16 kernel: timing kinds 128 + mode * 8 + cfg.
+// fp32 3x3 stride-1 fwd / dgrad on the split-bf16 kernel.  cfg 0 / 5: BN 128 / 96 on 8 x 32
+// output tiles; 6 / 1 / 2 / 3: BN 128 / 96 / 64 / 32 on 4 x 32; 4: BN 128 single-buffered
+// (x3_nb1); 7: the three BN 64 forms of of_set_tuning key 36.
 template <int MODE>
-int launch_tile_x3(const GemmArgs& a, hipStream_t s, double flops) {
+Launch tile_x3_launch(const GemmArgs& a) {
+  static const Launch T[7] = {
+      tile_x3_rec<128, 4, 2, MODE, X3_TH0>(), tile_x3_rec<96, 2, 3, MODE, 4>(),
+      tile_x3_rec<64, 4, 2, MODE, 4>(), tile_x3_rec<32, 4, 1, MODE, 4>(),
+      tile_x3_rec<128, 2, 2, MODE, 4, 1>(), tile_x3_rec<96, 4, 3, MODE, X3_TH0>(),
+      tile_x3_rec<128, 2, 4, MODE, 4>()};
+  static const Launch T7[3] = {tile_x3_rec<64, 4, 1, MODE, X3_TH0, 1>(),   // key 36 = 1, tall
+                               tile_x3_rec<64, 4, 1, MODE, 4, 1>(),        // key 36 = 2
+                               tile_x3_rec<64, 2, 2, MODE, 4, 1>()};       // key 36 = 3
   const int bn = a.bn_tile ? a.bn_tile : pick_bn(a.N);
-  dim3 grid(a.tiles_total * a.splits), block(256);
-  const bool tall = a.bm == X3_TH0 * TF_W;
-  const int cfg = bn == 128 ? (tall ? 0 : x3_nb1(a) ? 4 : 6)
-                            : bn == 96 ? (tall ? 5 : 1)
-                            : bn == 64 ? (tall || g_x3_bn64 >= 2 ? 7 : 2) : 3;
-  if (timing_on()) timing_begin(s);
-  if (cfg == 7) {                         // of_set_tuning key 36
-    if (tall) hipLaunchKernelGGL((conv_tile_x3<64, 4, 1, MODE, X3_TH0, 1>), grid, block, 0, s, a);
-    else if (g_x3_bn64 == 2) hipLaunchKernelGGL((conv_tile_x3<64, 4, 1, MODE, 4, 1>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_tile_x3<64, 2, 2, MODE, 4, 1>), grid, block, 0, s, a);
-  } else if (cfg == 0) hipLaunchKernelGGL((conv_tile_x3<128, 4, 2, MODE, X3_TH0>), grid, dim3(512), 0, s, a);
-  else if (cfg == 4) hipLaunchKernelGGL((conv_tile_x3<128, 2, 2, MODE, 4, 1>), grid, block, 0, s, a);
-  else if (cfg == 6) hipLaunchKernelGGL((conv_tile_x3<128, 2, 4, MODE, 4>), grid, dim3(512), 0, s, a);
-  else if (cfg == 5) hipLaunchKernelGGL((conv_tile_x3<96, 4, 3, MODE, X3_TH0>), grid, dim3(768), 0, s, a);
-  else if (cfg == 1) hipLaunchKernelGGL((conv_tile_x3<96, 2, 3, MODE, 4>), grid, dim3(384), 0, s, a);
-  else if (cfg == 2) hipLaunchKernelGGL((conv_tile_x3<64, 4, 2, MODE, 4>), grid, dim3(512), 0, s, a);
-  else hipLaunchKernelGGL((conv_tile_x3<32, 4, 1, MODE, 4>), grid, block, 0, s, a);
-  if (timing_on()) timing_end(s, 128 + MODE * 8 + cfg, flops);
-  int st = check_launch("conv_tile_x3");
-  if (st || a.splits == 1) return st;
-  return launch_splitk_epilogue<MODE>(a, s);
+  const bool tall = tall_tile(a);
+  if (bn == 64 && (tall || g_x3_bn64 >= 2))
+    return with_cfg(T7[tall ? 0 : g_x3_bn64 == 2 ? 1 : 2], 7);
+  const int cfg = bn == 128 ? (tall ? 0 : x3_nb1(a) ? 4 : 6) : bn == 96 ? (tall ? 5 : 1) : bn == 64 ? 2 : 3;
+  return with_cfg(T[cfg], cfg);
 }
 
-// bf16 3x3 stride-1 fwd / dgrad on conv_tile_b16: timing kinds 192 + mode * 8 + cfg (the
-// conv_tile_x3 configurations; cfg 4, the single-buffered one, is not used).
+// bf16 3x3 stride-1 fwd / dgrad on conv_tile_b16: the conv_tile_x3 configurations (cfg 4, the
+// single-buffered one, is not used).
 template <int MODE>
-int launch_tile_b16(const GemmArgs& a, hipStream_t s, double flops) {
-  const int bn = pick_bn(a.N);
-  dim3 grid(a.tiles_total * a.splits);
-  const bool tall = a.bm == X3_TH0 * TF_W;
-  const int cfg = bn == 128 ? (tall ? 0 : 6) : bn == 96 ? (tall ? 5 : 1) : bn == 64 ? 2 : 3;
-  if (timing_on()) timing_begin(s);
-  if (cfg == 0) hipLaunchKernelGGL((conv_tile_b16<128, 4, 2, MODE, X3_TH0>), grid, dim3(512), 0, s, a);
-  else if (cfg == 6) hipLaunchKernelGGL((conv_tile_b16<128, 2, 4, MODE, 4>), grid, dim3(512), 0, s, a);
-  else if (cfg == 5) hipLaunchKernelGGL((conv_tile_b16<96, 4, 3, MODE, X3_TH0>), grid, dim3(768), 0, s, a);
-  else if (cfg == 1) hipLaunchKernelGGL((conv_tile_b16<96, 2, 3, MODE, 4>), grid, dim3(384), 0, s, a);
-  else if (cfg == 2) hipLaunchKernelGGL((conv_tile_b16<64, 4, 2, MODE, 4>), grid, dim3(512), 0, s, a);
-  else hipLaunchKernelGGL((conv_tile_b16<32, 4, 1, MODE, 4>), grid, dim3(256), 0, s, a);
-  if (timing_on()) timing_end(s, 192 + MODE * 8 + cfg, flops);
-  int st = check_launch("conv_tile_b16");
-  if (st || a.splits == 1) return st;
-  return launch_splitk_epilogue<MODE>(a, s);
-}
-
-// bf16 3x3 stride-1 fwd / dgrad on conv_tile_ws: timing kinds 224 + mode * 8 + cfg
-// (0: BN 128, 1: BN 96; 8 x 32 output tiles, 4 compute + 4 staging waves).
-template <int MODE>
-int launch_tile_ws(const GemmArgs& a, hipStream_t s, double flops) {
-  if (timing_on()) timing_begin(s);
-  int st = launch_tile_ws_kernel(a, MODE, s);
-  if (timing_on()) timing_end(s, 224 + MODE * 8 + (pick_bn(a.N) == 128 ? 0 : 1), flops);
-  if (st || a.splits == 1) return st;
-  return launch_splitk_epilogue<MODE>(a, s);
+Launch tile_b16_launch(const GemmArgs& a) {
+  static const Launch T[7] = {
+      tile_b16_rec<128, 4, 2, MODE, X3_TH0>(), tile_b16_rec<96, 2, 3, MODE, 4>(),
+      tile_b16_rec<64, 4, 2, MODE, 4>(), tile_b16_rec<32, 4, 1, MODE, 4>(), Launch{},
+      tile_b16_rec<96, 4, 3, MODE, X3_TH0>(), tile_b16_rec<128, 2, 4, MODE, 4>()};
+  const int bn = bn_cfg(a.N);
+  const int cfg = bn == 0 ? (tall_tile(a) ? 0 : 6) : bn == 1 ? (tall_tile(a) ? 5 : 1) : bn;
+  return with_cfg(T[cfg], cfg);
 }
 
 // fp32 implicit GEMM on the split-bf16 kernel (conv_gemm_x3, every non-3x3-stride-1 shape):
 // BN 128 (8 waves of 32 x 64) for N > 64, else 256 x 64 tiles; one workgroup per CU, so K
-// splits come from the cost model of tile_args (rounds of 256 workgroups x (chunks per slice
-// + 1) + half a chunk per slice and tile round for the slab pass).  Timing kinds 160 + 8 mode
-// + (0: 128 x 128, 1: 256 x 64).
+// splits come from best_split().
 void gemm_x3_plan(GemmArgs& a) {
   const int bm = a.N > 64 ? 128 : 256, bn = a.N > 64 ? 128 : 64;
   int tiles = 0, tiles_all = 0, kmax = 0;
@@ -5267,19 +5292,7 @@ void gemm_x3_plan(GemmArgs& a) {
   // in-place form (fewer tiles, fewer slab rows) too
   const int64_t plan_tiles = (int64_t)tiles_all * a.n_tiles;
   const int chunks = (int)cdiv(kmax, BKH);
-  int best = 1;
-  double best_cost = 1e30;
-  for (int sp = 1; sp <= std::min(8, chunks); ++sp) {
-    const int per = (int)cdiv(chunks, sp);
-    if (cdiv(chunks, per) != sp) continue;
-    const int64_t w = plan_tiles * sp;
-    const double cost = (double)cdiv(w, device_cus()) * (per + 1.0) +
-                        (sp > 1 ? 0.1 * g_x3g_ep * sp * plan_tiles / (double)device_cus() : 0.0);
-    if (cost < best_cost - 1e-9) {
-      best_cost = cost;
-      best = sp;
-    }
-  }
+  const int best = best_split(chunks, plan_tiles, device_cus(), g_x3g_ep);
   a.k_per_split = (int)cdiv(chunks, best) * BKH;
   a.splits = (int)cdiv(kmax, a.k_per_split);
 }
@@ -5291,26 +5304,35 @@ void gemm_x3_plan(GemmArgs& a) {
 // Measured (tools/conv_bench.py, one box): enc.l3.c0 fwd 81 / 84 / 71 us for 0 / 1 / 2,
 // enc.l4.c0 fwd 69 / 72 / 60, dgrad 77 / 79 / 69; the bench step even (626-628 pairs/s).
 static int g_gx3_ring = 2;
-// (NP = 1, the bf16 form: timing kinds 240 + mode * 8 + cfg)
+// conv_gemm_x3 / conv_wgrad_x3: __launch_bounds__(64 * WAVES_M * WAVES_N, ...); NP = 1 is the
+// bf16 form (kinds KIND_GEMM_B16)
+template <int BM, int BN, int WM, int WN, int MODE, int NP, int RING>
+constexpr Launch gemm_x3_rec() {
+  return {conv_gemm_x3<BM, BN, WM, WN, MODE, NP, RING>, 64 * WM * WN,
+          kind(NP == 1 ? KIND_GEMM_B16 : KIND_GEMM_X3, MODE, 0), "conv_gemm_x3"};
+}
+template <int BM, int BN, int WM, int WN, int NP>
+constexpr Launch wgrad_x3_rec() {
+  return {conv_wgrad_x3<BM, BN, WM, WN, NP>, 64 * WM * WN,
+          kind(NP == 1 ? KIND_GEMM_B16 : KIND_GEMM_X3, MODE_WGRAD, 0),
+          NP == 1 ? "conv_wgrad_x3_b16" : "conv_wgrad_x3"};
+}
+// [key 30][cfg]: cfg 0: 128 x 128 (N > 64), 1: 256 x 64
 template <int MODE, int NP = 3>
-int launch_gemm_x3(const GemmArgs& a, hipStream_t s, double flops) {
+Launch gemm_x3_launch(const GemmArgs& a) {
+  static const Launch T[3][2] = {
+      {gemm_x3_rec<128, 128, 4, 2, MODE, NP, 0>(), gemm_x3_rec<256, 64, 8, 1, MODE, NP, 0>()},
+      {gemm_x3_rec<128, 128, 4, 2, MODE, NP, 3>(), gemm_x3_rec<256, 64, 8, 1, MODE, NP, 3>()},
+      {gemm_x3_rec<128, 128, 4, 2, MODE, NP, 2>(), gemm_x3_rec<256, 64, 8, 1, MODE, NP, 2>()}};
   const int cfg = a.N > 64 ? 0 : 1;
-  dim3 grid(a.tiles_total * a.splits), block(512);
-  if (timing_on()) timing_begin(s);
-  if (g_gx3_ring == 1) {
-    if (cfg == 0) hipLaunchKernelGGL((conv_gemm_x3<128, 128, 4, 2, MODE, NP, 3>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_gemm_x3<256, 64, 8, 1, MODE, NP, 3>), grid, block, 0, s, a);
-  } else if (g_gx3_ring == 2) {
-    if (cfg == 0) hipLaunchKernelGGL((conv_gemm_x3<128, 128, 4, 2, MODE, NP, 2>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_gemm_x3<256, 64, 8, 1, MODE, NP, 2>), grid, block, 0, s, a);
-  } else {
-    if (cfg == 0) hipLaunchKernelGGL((conv_gemm_x3<128, 128, 4, 2, MODE, NP, 0>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_gemm_x3<256, 64, 8, 1, MODE, NP, 0>), grid, block, 0, s, a);
-  }
-  if (timing_on()) timing_end(s, (NP == 1 ? 240 : 160) + MODE * 8 + cfg, flops);
-  int st = check_launch("conv_gemm_x3");
-  if (st || a.splits == 1) return st;
-  return launch_splitk_epilogue<MODE>(a, s);
+  return with_cfg(T[g_gx3_ring][cfg], cfg);
+}
+// cfg 0: 128 x 128 (Cout > 64), 1: 128 x 64
+template <int NP>
+Launch wgrad_x3_launch(const of_conv_desc* d) {
+  static const Launch T[2] = {wgrad_x3_rec<128, 128, 4, 2, NP>(), wgrad_x3_rec<128, 64, 4, 2, NP>()};
+  const int cfg = d->cout > 64 ? 0 : 1;
+  return with_cfg(T[cfg], cfg);
 }
 
 // bf16 3x3 stride-1 wgrad on conv_wgrad_tile_bf16: block channel tiles (CIB x COB).
@@ -5380,70 +5402,206 @@ static int g_gemm_b16 = 6;
 // of_set_tuning key 17: conv_wgrad_tile_bf16 with software-pipelined fragments (1, default)
 // or the round-1 per-row reads (0).
 static int g_wgt_pf = 1;
-bool gemm_b16_wg(const of_conv_desc* d) {
-  return (g_gemm_b16 & 4) && !narrow_ok(d) && !tile_ok(d) && !(stem_wg_ok(d) && g_stem_bf16);
+
+// ---- one path decision per call -----------------------------------------------------------
+// The kernel family of a forward / input-gradient call and of a weight gradient.  The
+// implementations switch on it, and the workspace queries plan the same family.
+enum class Fam { narrow, gemm_f32, gemm_bf16, gemm_x3, gemm_b16, tile_bf16, tile_x3, tile_b16,
+                 tile_ws, stem };
+enum class WFam { narrow, stem, tile_x3, tile_b16, gemm_x3, gemm_b16, tile, gemm_bf16, gemm_f32 };
+
+// prec: 0 fp32 MFMA, 1 bf16, 2 fp32 on the split-bf16 kernels.  The implicit GEMM of the
+// shapes without a tile kernel: conv_gemm_x3 with three planes, or for bf16 with one (key 16).
+Fam gemm_family(int prec, int mode) {
+  if (!prec) return Fam::gemm_f32;
+  if (prec == 2) return Fam::gemm_x3;
+  return (g_gemm_b16 & (mode == MODE_FWD ? 1 : 2)) ? Fam::gemm_b16 : Fam::gemm_bf16;
+}
+Fam tile_family(const of_conv_desc* d, int prec, int mode, bool bnp = false) {
+  if (prec == 2) return Fam::tile_x3;
+  if (ws_ok(d, mode)) return Fam::tile_ws;
+  // (bf16 with BN partial sums and key 32: conv_tile_b16, the split body with one plane)
+  return g_tile_b16 == 1 || (bnp && g_bnp_b16) ? Fam::tile_b16 : Fam::tile_bf16;
+}
+// plain: no BN, residual or z (the Cout <= 4 VALU kernel's epilogue); stem_kernel = false
+// plans what runs when conv_stem_x3's float4 epilogue does not fit the call's strides.
+Fam fwd_family(const of_conv_desc* d, int prec, bool plain, bool stem_kernel = true) {
+  if (!prec) return narrow_ok(d) && plain ? Fam::narrow : Fam::gemm_f32;
+  if (tile_ok(d)) return tile_family(d, prec, MODE_FWD);
+  if (stem_kernel && (prec == 2 || g_stem_bf16) && g_stem_x3 && stem_x3_ok(d)) return Fam::stem;
+  return gemm_family(prec, MODE_FWD);
+}
+Fam dgrad_family(const of_conv_desc* d, int prec, bool bnp = false) {
+  if (!prec) return narrow_ok(d) ? Fam::narrow : Fam::gemm_f32;
+  return tile_ok(d) ? tile_family(d, prec, MODE_DGRAD, bnp) : gemm_family(prec, MODE_DGRAD);
 }
 
-WgradPlan wgrad_plan(const of_conv_desc* d, bool bf16 = false, bool x3 = false) {
+// The GEMM a family runs for (d, mode), planned: tiles, groups and K slices -- everything the
+// workspace depends on.  (conv_stem_x3 is planned as the GEMM that replaces it.)
+GemmArgs plan_args(const of_conv_desc* d, const Geo& g, int mode, Fam f, bool in_place = false) {
+  if (f == Fam::tile_bf16 || f == Fam::tile_x3 || f == Fam::tile_b16 || f == Fam::tile_ws)
+    return tile_args(d, g, mode, f == Fam::tile_x3, f == Fam::tile_b16, f == Fam::tile_ws);
+  const bool k16 = f != Fam::gemm_f32 && f != Fam::narrow;   // K padded for the bf16 images
+  GemmArgs a = mode == MODE_FWD ? fwd_args(d, g, k16) : dgrad_args(d, g, k16, in_place);
+  if (f == Fam::gemm_x3 || f == Fam::gemm_b16) gemm_x3_plan(a);
+  return a;
+}
+
+template <int MODE>
+int launch_family(Fam f, const GemmArgs& a, hipStream_t s, double flops) {
+  switch (f) {
+    case Fam::tile_x3: return launch<MODE>(tile_x3_launch<MODE>(a), a, s, flops);
+    case Fam::tile_ws:   // (conv_ws.hip holds the table, its kinds the bare cfg: add the base)
+      return launch<MODE>(with_cfg(tile_ws_launch(a, MODE), kind(KIND_TILE_WS, MODE, 0)), a, s, flops);
+    case Fam::tile_b16: return launch<MODE>(tile_b16_launch<MODE>(a), a, s, flops);
+    case Fam::tile_bf16: return launch<MODE>(tile_bf16_launch<MODE>(a), a, s, flops);
+    case Fam::gemm_x3: return launch<MODE>(gemm_x3_launch<MODE>(a), a, s, flops);
+    case Fam::gemm_b16: return launch<MODE>(gemm_x3_launch<MODE, 1>(a), a, s, flops);
+    case Fam::gemm_bf16: return launch<MODE>(gemm_bf16_launch<MODE>(a), a, s, flops);
+    case Fam::gemm_f32: return launch<MODE>(gemm_f32_launch<MODE>(a), a, s, flops);
+    default: return fail(OF_EINVAL, "conv: no GEMM launch for this family");
+  }
+}
+
+// The stem's kernel wherever it fits (key 14; bf16: key 15); else 3x3 stride 1 on the tile
+// kernels (bf16: key 13; fp32 split: where wgx3_ok); else the one- / three-plane implicit GEMM
+// (keys 16 / 6), the fp32 / bf16 tile kernels (wgt_ok) or the MFMA GEMMs.
+WFam wgrad_family(const of_conv_desc* d, int prec) {
+  const bool bf16 = prec == 1;
+  if (narrow_ok(d)) return WFam::narrow;
+  if (stem_wg_ok(d) && (!bf16 || g_stem_bf16)) return WFam::stem;
+  if (prec == 2 && wgx3_ok(d)) return WFam::tile_x3;
+  if (bf16 && g_wgrad_b16 && wgx3_ok(d)) return WFam::tile_b16;
+  if (prec == 2 && g_wgx3_gemm) return WFam::gemm_x3;
+  if (bf16 && (g_gemm_b16 & 4) && !tile_ok(d)) return WFam::gemm_b16;
+  if (wgt_ok(d, bf16)) return WFam::tile;
+  return bf16 ? WFam::gemm_bf16 : WFam::gemm_f32;
+}
+
+// The tile weight gradients' K (pixel tiles) and grid (channel-block tiles): conv_wgrad_tile_x3
+// / _x3b / _b16 by wgx3_cfg, conv_wgrad_tile_bf16 / _f32 (x3 = false) by wgt_cfg.
+void wgrad_tiles(GemmArgs& a, const of_conv_desc* d, const Geo& g, bool x3) {
+  int cib, cob;
+  x3 ? wgx3_blocks(d, cib, cob) : wgt_blocks(d, cib, cob);
+  a.K = d->n * (int)cdiv(d->ho, x3 ? wgx3_rows(wgx3_cfg(d)) : TT_H) * (int)cdiv(d->wo, TT_W);
+  a.n_tiles = (int)cdiv(d->cout, cob);
+  a.tiles_total = (int)cdiv(g.cin_p, cib) * a.n_tiles;
+}
+
+// The split-K plan of a weight gradient (callers handle WFam::narrow).
+WgradPlan wgrad_plan(const of_conv_desc* d, int prec) {
   Geo g = geo(d);
+  const WFam f = wgrad_family(d, prec);
   WgradPlan p;
   p.M = g.taps * g.cin_p;
   p.ldc = g.cout_p;
   p.split_stride = (int64_t)(p.M + 1) * p.ldc;   // + one row for the bias column sums
-  if (stem_wg_ok(d) && (!bf16 || g_stem_bf16)) {
-    // conv_wgrad_stem_x3: K = 4 x 32 output tiles, persistent workgroups (3 per CU)
-    const int T = stem_wg_tiles(d);
-    int splits = std::max(1, std::min(T, SW_WGS_PER_CU * device_cus()));
-    p.k_per_split = (int)cdiv(T, splits);
-    p.splits = (int)cdiv(T, p.k_per_split);
+  // `splits` equal slices of `units` of K, each a multiple of `step`
+  auto slice = [&p](int units, int splits, int step = 1) {
+    p.k_per_split = (int)round_up(cdiv(units, std::max(1, splits)), step);
+    p.splits = (int)cdiv(units, p.k_per_split);
     return p;
+  };
+  if (f == WFam::stem)   // K = 4 x 32 output tiles, persistent workgroups (3 per CU)
+    return slice(stem_wg_tiles(d), std::min(stem_wg_tiles(d), SW_WGS_PER_CU * device_cus()));
+  if (f == WFam::tile_x3 || f == WFam::tile_b16 || f == WFam::tile) {
+    // K = 4 x 16 (conv_wgrad_tile_bf16 / _f32: 8 x 16) pixel tiles; one workgroup per CU
+    // (LDS-bound occupancy), equal slices, of at least g_wgx3_min_tiles tiles for the 9-tap forms
+    GemmArgs t{};
+    wgrad_tiles(t, d, g, f != WFam::tile);
+    const int splits = std::min(t.K, device_cus() / t.tiles_total);
+    return slice(t.K, f == WFam::tile ? splits : std::min(splits, t.K / g_wgx3_min_tiles));
   }
-  if ((x3 || (bf16 && g_wgrad_b16)) && wgx3_ok(d)) {
-    // K = 4 x 16 pixel tiles; one workgroup per CU, equal slices
-    int cib, cob;
-    wgx3_blocks(d, cib, cob);
-    const int chan_tiles = (int)(cdiv(g.cin_p, cib) * cdiv(d->cout, cob));
-    const int T = d->n * (int)cdiv(d->ho, wgx3_rows(wgx3_cfg(d))) * (int)cdiv(d->wo, TT_W);
-    int splits = std::max(1, std::min(T, device_cus() / chan_tiles));
-    splits = std::max(1, std::min(splits, T / g_wgx3_min_tiles));
-    p.k_per_split = (int)cdiv(T, splits);
-    p.splits = (int)cdiv(T, p.k_per_split);
-    return p;
-  }
-  const bool g16 = bf16 && gemm_b16_wg(d);
-  if ((x3 || g16) && !narrow_ok(d)) {
+  const int K = d->n * d->ho * d->wo;
+  if (f == WFam::gemm_x3 || f == WFam::gemm_b16) {
     // conv_wgrad_x3: 128 x (128 | 64) tiles, one workgroup per CU (two for the one-plane bf16
     // form); K = output pixels in 32-pixel chunks, split to fill the CUs with at least 8
     // chunks per slice
-    const int K = d->n * d->ho * d->wo;
     const int tiles = (int)(cdiv(p.M, 128) * cdiv(d->cout, d->cout > 64 ? 128 : 64));
-    int splits = std::max(1, (g16 ? 2 : 1) * device_cus() / tiles);
-    splits = std::min(splits, (int)std::max<int64_t>(1, cdiv(K, 8 * BKH)));
-    p.k_per_split = (int)round_up(cdiv(K, splits), BKH);
-    p.splits = (int)cdiv(K, p.k_per_split);
-    return p;
+    const int splits = std::max(1, (f == WFam::gemm_b16 ? 2 : 1) * device_cus() / tiles);
+    return slice(K, std::min(splits, (int)std::max<int64_t>(1, cdiv(K, 8 * BKH))), BKH);
   }
-  if (wgt_ok(d, bf16)) {
-    // K = 8 x 16 pixel tiles; one workgroup per CU (LDS-bound occupancy), equal slices
-    int cib, cob;
-    wgt_blocks(d, cib, cob);
-    const int chan_tiles = (int)(cdiv(g.cin_p, cib) * cdiv(d->cout, cob));
-    const int T = d->n * (int)cdiv(d->ho, TT_H) * (int)cdiv(d->wo, TT_W);
-    int splits = std::max(1, std::min(T, device_cus() / chan_tiles));
-    p.k_per_split = (int)cdiv(T, splits);
-    p.splits = (int)cdiv(T, p.k_per_split);
-    return p;
-  }
-  const int bk = bf16 ? BKH : BK;
-  const int K = d->n * d->ho * d->wo;
+  const int bk = prec == 1 ? BKH : BK;
   const int tiles = (int)(cdiv(p.M, pick_bm(d->cout)) * cdiv(d->cout, pick_bn(d->cout)));
   // Fill up to g_wgrad_wgs (4) workgroups per CU without overshooting a multiple of the CU
   // count (an overshoot leaves a few CUs with one extra long-running workgroup: a tail).
-  int splits = std::max(1, (g_wgrad_wgs * device_cus()) / tiles);
-  splits = std::min(splits, (int)std::max<int64_t>(1, cdiv(K, 8 * bk)));
-  p.k_per_split = (int)round_up(cdiv(K, splits), bk);
-  p.splits = (int)cdiv(K, p.k_per_split);
-  return p;
+  const int splits = std::max(1, (g_wgrad_wgs * device_cus()) / tiles);
+  return slice(K, std::min(splits, (int)std::max<int64_t>(1, cdiv(K, 8 * bk))), bk);
+}
+size_t wgrad_workspace(const of_conv_desc* d, int prec) {
+  if (validate(d) != OF_OK) return 0;
+  if (narrow_ok(d)) return narrow_wgrad_ws(d);
+  const WgradPlan p = wgrad_plan(d, prec);
+  return (size_t)p.splits * p.split_stride * sizeof(float);
+}
+
+// ---- the weight gradients' launch tables ----------------------------------------------------
+// conv_wgrad_stem_x3: __launch_bounds__(SW_NT, 3); one workgroup per K slice
+template <int NP, bool FUSED = false>
+constexpr Launch wgrad_stem_rec() {
+  return {conv_wgrad_stem_x3<NP, FUSED>, SW_NT, NP == 1 ? KIND_STEM_WG_B16 : KIND_STEM_WG_X3,
+          FUSED ? "conv_wgrad_stem_x3 fused" : "conv_wgrad_stem_x3"};
+}
+// conv_wgrad_tile_x3: __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1)
+template <int CI, int CO, int R, int XH>
+constexpr Launch wgrad_tile_x3_rec() {
+  return {conv_wgrad_tile_x3<CI, CO, R, XH>, 64 * CI * CO * R, kind(KIND_TILE_X3, MODE_WGRAD, 0),
+          "conv_wgrad_tile_x3"};
+}
+// conv_wgrad_tile_x3b / _b16 and their _c3 forms: __launch_bounds__(64 * WAVES_CI * WAVES_CO, 1);
+// STAGE is of_set_tuning key 40 (0: the _c3 kernels)
+template <int STAGE, int CI, int CO, int XH, int MI = 1>
+constexpr Launch wgrad_x3b_rec() {
+  return {STAGE ? conv_wgrad_tile_x3b<CI, CO, XH, MI> : conv_wgrad_tile_x3b_c3<CI, CO, XH, MI>,
+          64 * CI * CO, KIND_WGRAD_X3B, "conv_wgrad_tile_x3"};
+}
+template <int STAGE, int CI, int CO, int XH>
+constexpr Launch wgrad_b16_rec() {
+  return {STAGE ? conv_wgrad_tile_b16<CI, CO, XH> : conv_wgrad_tile_b16_c3<CI, CO, XH>,
+          64 * CI * CO, KIND_WGRAD_B16, "conv_wgrad_tile_b16"};
+}
+// conv_wgrad_tile_bf16 / _f32: __launch_bounds__(256, 1)
+template <int CI, int CO, int PF = 1>
+constexpr Launch wgrad_tile_bf16_rec() {
+  return {conv_wgrad_tile_bf16<CI, CO, PF>, 256, kind(KIND_TILE_BF16, MODE_WGRAD, 0), "conv_wgrad_tile"};
+}
+template <int CI, int CO>
+constexpr Launch wgrad_tile_f32_rec() {
+  return {conv_wgrad_tile_f32<CI, CO>, 256, kind(KIND_TILE_F32, MODE_WGRAD, 0), "conv_wgrad_tile"};
+}
+
+// fp32 3x3 stride-1 weight gradient by wgx3_cfg: the 9-tap form (key 4) [key 40][key 5 - 1][cfg]
+// with waves of 16 MI ci x 32 / MI co, or the 3-tap form (cfg 0-3).
+Launch wgrad_tile_x3_launch(int cfg) {
+  static const Launch B[2][2][5] = {
+      {{wgrad_x3b_rec<0, 2, 4, 8>(), wgrad_x3b_rec<0, 2, 3, 8>(), wgrad_x3b_rec<0, 4, 2, 4>(),
+        wgrad_x3b_rec<0, 4, 1, 4>(), wgrad_x3b_rec<0, 2, 2, 8>()},
+       {wgrad_x3b_rec<0, 1, 8, 8, 2>(), wgrad_x3b_rec<0, 1, 6, 8, 2>(), wgrad_x3b_rec<0, 2, 4, 4, 2>(),
+        wgrad_x3b_rec<0, 2, 2, 4, 2>(), wgrad_x3b_rec<0, 1, 4, 8, 2>()}},
+      {{wgrad_x3b_rec<1, 2, 4, 8>(), wgrad_x3b_rec<1, 2, 3, 8>(), wgrad_x3b_rec<1, 4, 2, 4>(),
+        wgrad_x3b_rec<1, 4, 1, 4>(), wgrad_x3b_rec<1, 2, 2, 8>()},
+       {wgrad_x3b_rec<1, 1, 8, 8, 2>(), wgrad_x3b_rec<1, 1, 6, 8, 2>(), wgrad_x3b_rec<1, 2, 4, 4, 2>(),
+        wgrad_x3b_rec<1, 2, 2, 4, 2>(), wgrad_x3b_rec<1, 1, 4, 8, 2>()}}};
+  static const Launch T[4] = {wgrad_tile_x3_rec<1, 4, 3, 8>(), wgrad_tile_x3_rec<1, 3, 3, 8>(),
+                              wgrad_tile_x3_rec<2, 2, 3, 4>(), wgrad_tile_x3_rec<2, 1, 3, 4>()};
+  const bool x3b = g_wgx3b == 2 || (g_wgx3b == 1 && cfg == 0) || cfg == 4;
+  return with_cfg(x3b ? B[g_wgx3b_stage][g_wgx3b_mi - 1][cfg] : T[cfg], cfg);
+}
+// bf16 on the 9-tap structure (key 13): the x3b configurations, [key 40][cfg]
+Launch wgrad_tile_b16_launch(int cfg) {
+  static const Launch T[2][5] = {
+      {wgrad_b16_rec<0, 2, 4, 8>(), wgrad_b16_rec<0, 2, 3, 8>(), wgrad_b16_rec<0, 4, 2, 4>(),
+       wgrad_b16_rec<0, 4, 1, 4>(), wgrad_b16_rec<0, 2, 2, 8>()},
+      {wgrad_b16_rec<1, 2, 4, 8>(), wgrad_b16_rec<1, 2, 3, 8>(), wgrad_b16_rec<1, 4, 2, 4>(),
+       wgrad_b16_rec<1, 4, 1, 4>(), wgrad_b16_rec<1, 2, 2, 8>()}};
+  return with_cfg(T[g_wgx3b_stage][cfg], cfg);
+}
+// conv_wgrad_tile_bf16 [key 17] / conv_wgrad_tile_f32, wgt_cfg 0: <1, 4>, 2: <2, 2>
+Launch wgrad_tile_launch(int cfg, bool bf16) {
+  static const Launch T16[2][2] = {{wgrad_tile_bf16_rec<1, 4, 0>(), wgrad_tile_bf16_rec<2, 2, 0>()},
+                                   {wgrad_tile_bf16_rec<1, 4>(), wgrad_tile_bf16_rec<2, 2>()}};
+  static const Launch T32[2] = {wgrad_tile_f32_rec<1, 4>(), wgrad_tile_f32_rec<2, 2>()};
+  return with_cfg(bf16 ? T16[g_wgt_pf != 0][cfg / 2] : T32[cfg / 2], cfg);
 }
 
 }  // namespace
@@ -5645,42 +5803,35 @@ int of_conv_pack_many(const void* dev_table, int64_t total_work, void* stream) {
   return check_launch("pack_many");
 }
 
-// Timing kind of the narrow (VALU) path; GEMM kinds are MODE * 8 + tile config (0..3).
-constexpr int KIND_NARROW = 7;
-constexpr int KIND_STEM_X3 = 184;   // conv_stem_x3 (bench.py kind_name)
-constexpr int KIND_STEM_B16 = 186;  // conv_stem_x3<32, 1> (bf16); 187: conv_wgrad_stem_x3<1>
-
 double conv_flops(const of_conv_desc* d) {
   return 2.0 * d->n * d->ho * d->wo * (double)d->cout * d->kh * d->kw * d->cin;
 }
 
 size_t of_conv2d_fwd_workspace(const of_conv_desc* d) {
   if (validate(d) != OF_OK) return 0;
-  return fd_workspace(fwd_args(d, geo(d)));
+  return fd_workspace(plan_args(d, geo(d), MODE_FWD, Fam::gemm_f32));
 }
 
 size_t of_conv2d_dgrad_workspace(const of_conv_desc* d) {
   if (validate(d) != OF_OK) return 0;
-  return fd_workspace(dgrad_args(d, geo(d)));
+  return fd_workspace(plan_args(d, geo(d), MODE_DGRAD, Fam::gemm_f32));
 }
 
+// (the larger of the conv_gemm_x3<..., 1> and the conv_gemm_bf16 plan: a buffer sized under one
+// value of key 16 serves the other)
 size_t of_conv2d_fwd_bf16_workspace(const of_conv_desc* d) {
   if (validate(d) != OF_OK) return 0;
-  if (tile_ok(d))
-    return fd_workspace(tile_args(d, geo(d), MODE_FWD, false, g_tile_b16 == 1, ws_ok(d, MODE_FWD)));
-  GemmArgs a = fwd_args(d, geo(d), true);
-  if (g_gemm_b16 & 1) gemm_x3_plan(a);
-  return std::max(fd_workspace(a), fd_workspace(fwd_args(d, geo(d), true)));
+  if (tile_ok(d)) return fd_workspace(plan_args(d, geo(d), MODE_FWD, tile_family(d, 1, MODE_FWD)));
+  return std::max(fd_workspace(plan_args(d, geo(d), MODE_FWD, gemm_family(1, MODE_FWD))),
+                  fd_workspace(plan_args(d, geo(d), MODE_FWD, Fam::gemm_bf16)));
 }
 
+// (the larger of the two plans, as the forward's)
 size_t of_conv2d_dgrad_bf16_workspace(const of_conv_desc* d) {
   if (validate(d) != OF_OK) return 0;
-  if (tile_ok(d))
-    return fd_workspace(tile_args(d, geo(d), MODE_DGRAD, false, g_tile_b16 == 1,
-                                  ws_ok(d, MODE_DGRAD)));
-  GemmArgs a = dgrad_args(d, geo(d), true);
-  if (g_gemm_b16 & 2) gemm_x3_plan(a);
-  return std::max(fd_workspace(a), fd_workspace(dgrad_args(d, geo(d), true)));
+  if (tile_ok(d)) return fd_workspace(plan_args(d, geo(d), MODE_DGRAD, tile_family(d, 1, MODE_DGRAD)));
+  return std::max(fd_workspace(plan_args(d, geo(d), MODE_DGRAD, gemm_family(1, MODE_DGRAD))),
+                  fd_workspace(plan_args(d, geo(d), MODE_DGRAD, Fam::gemm_bf16)));
 }
 
 int of_conv_path(const of_conv_desc* d) {
@@ -5707,34 +5858,33 @@ static int conv_fwd_impl(int prec, const of_conv_desc* d, const float* x, int ld
   OF_CHECK_ARG(!z || ldz >= d->cout, "conv fwd: ldz");
   OF_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)w_fwd & 15) == 0,
                "conv fwd: x / w must be 16-byte aligned");
-  if (!prec && narrow_ok(d) && !bn_gamma && !residual && !z) {   // 2-channel layers: VALU
+  Fam f = fwd_family(d, prec, !bn_gamma && !residual && !z);
+  if (f == Fam::narrow) {                                     // 2-channel layers: VALU
     hipStream_t s = as_stream(stream);
     if (timing_on()) timing_begin(s);
     st = narrow_fwd(d, x, ldx, static_cast<const float*>(w_fwd), bias, act, alpha, y, ldy, s);
-    if (timing_on()) timing_end(s, MODE_FWD * 8 + KIND_NARROW, conv_flops(d));
+    if (timing_on()) timing_end(s, kind(KIND_F32, MODE_FWD, KIND_NARROW), conv_flops(d));
     return st;
   }
   Geo g = geo(d);
-  const bool tile = (bf16 || x3) && tile_ok(d);
-  const bool ws = tile && bf16 && ws_ok(d, MODE_FWD);
-  const bool b16 = tile && bf16 && g_tile_b16 == 1;
-  GemmArgs a = tile ? tile_args(d, g, MODE_FWD, x3, b16, ws) : fwd_args(d, g, bf16 || x3);
-  bool stem = (x3 || (bf16 && g_stem_bf16)) && !tile && g_stem_x3 && stem_x3_ok(d);
-  if (stem) {                            // conv_stem_x3: one workgroup per output tile, no split
-    a.splits = 1;
-    a.k_per_split = a.K;
-    a.slab = nullptr;
-  }
-  a.C = y;   // (vec_ep_ok reads the output fields)
+  GemmArgs a = plan_args(d, g, MODE_FWD, f);
+  a.C = y;
   a.ldc = ldy;
   a.res = residual;
   a.ldr = ldr;
   a.z = z;
   a.ldz = ldz;
-  stem = stem && vec_ep_ok(a);
-  const bool g16 = bf16 && !tile && !stem && (g_gemm_b16 & 1);   // conv_gemm_x3<..., 1>
-  if ((x3 || g16) && !tile && !stem) gemm_x3_plan(a);
-  if (!stem) attach_slab(a, workspace, ws_bytes, tile ? 1 : (bf16 || x3) ? BKH : BK);
+  if (f == Fam::stem) {                  // conv_stem_x3: one workgroup per output tile, no split
+    a.splits = 1;
+    a.k_per_split = a.K;
+    a.slab = nullptr;
+    if (!vec_ep_ok(a)) {                 // float4 epilogue only: else the implicit GEMM
+      f = gemm_family(prec, MODE_FWD);
+      if (f != Fam::gemm_bf16) gemm_x3_plan(a);   // (conv_gemm_bf16 keeps the one K slice)
+    }
+  }
+  const bool tile = prec && tile_ok(d);
+  if (f != Fam::stem) attach_slab(a, workspace, ws_bytes, tile ? 1 : prec ? BKH : BK);
   a.A = x;
   a.lda = ldx;
   a.a_bytes = (int64_t)d->n * d->h * d->w * ldx * 4;
@@ -5743,60 +5893,42 @@ static int conv_fwd_impl(int prec, const of_conv_desc* d, const float* x, int ld
   a.b_bytes = x3 ? 3 * a.b_plane * 2 : bf16 ? a.b_plane * 2 : (int64_t)g.kf * g.nf * 4;
   OF_CHECK_ARG(a.a_bytes < INT32_MAX && a.b_bytes < INT32_MAX,
                "conv fwd: tensors must be < 2 GiB (32-bit buffer offsets)");
-  a.C = y;
-  a.ldc = ldy;
   a.bias = bias;
   a.bn_g = bn_gamma;
   a.bn_b = bn_beta;
   a.bn_m = bn_mean;
   a.bn_v = bn_var;
   a.bn_eps = bn_eps;
-  a.res = residual;
-  a.ldr = ldr;
-  a.z = z;
-  a.ldz = ldz;
   a.act = act;
   a.alpha = alpha;
   hipStream_t s = as_stream(stream);
   const double flops = 2.0 * d->n * d->ho * d->wo * (double)d->cout * g.taps * d->cin;
   a.vec_ep = vec_ep_ok(a);
   // split 3x3 forward, one K slice, fp32 output only: the direct epilogue (conv_dev.h)
-  a.direct16 = x3 && tile && (g_x3_direct & 1) && a.splits == 1 && a.vec_ep && !residual && !z &&
-               d->cout % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)y & 15) == 0;
+  a.direct16 = f == Fam::tile_x3 && (g_x3_direct & 1) && a.splits == 1 && a.vec_ep && !residual &&
+               !z && d->cout % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)y & 15) == 0;
   if (pool) {
-    if (!stem || d->ho % 2 || d->wo % 2 || d->cout % 4)
+    if (f != Fam::stem || d->ho % 2 || d->wo % 2 || d->cout % 4)
       return fail(OF_EUNSUPPORTED, "conv fwd pool: only the stem kernel with an even output");
     OF_CHECK_ARG(((uintptr_t)pool & 15) == 0, "conv fwd pool: 16-byte alignment");
     a.pool_out = pool;
   }
-  if (stem) {
-    const int64_t tiles = (int64_t)d->n * cdiv(d->ho, ST_TH) * cdiv(d->wo, ST_TW);
-    OF_CHECK_ARG(tiles < INT32_MAX, "conv stem: too many tiles");
-    if (timing_on()) timing_begin(s);
-    // persistent (of_set_tuning key 31 = workgroups per CU, default as many as the LDS holds:
-    // 2 fp32 / 3 bf16 / 1 for the 64-channel form; 0: one tile per workgroup, the round-2..4
-    // grid): B staged once per workgroup, the next tile's halo loaded during this tile's MFMAs
-    const int groups = bf16 || g_stem_x3 != 2 ? 2 : 1;
-    const int per_cu = g_stem_persist < 0 ? (bf16 ? 3 : g_stem_x3 == 2 ? 1 : 2) : g_stem_persist;
-    const int64_t cap = per_cu > 0 ? (int64_t)per_cu * device_cus() : tiles * groups;
-    const unsigned grid = (unsigned)(std::min(tiles * groups, cap) / groups * groups);
-    if (bf16)
-      hipLaunchKernelGGL((conv_stem_x3<32, 1>), dim3(grid), dim3(256), 0, s, a, (int)tiles);
-    else if (g_stem_x3 == 2)
-      hipLaunchKernelGGL(conv_stem_x3<64>, dim3(grid), dim3(512), 0, s, a, (int)tiles);
-    else
-      hipLaunchKernelGGL(conv_stem_x3<32>, dim3(grid), dim3(256), 0, s, a, (int)tiles);
-    if (timing_on()) timing_end(s, bf16 ? KIND_STEM_B16 : KIND_STEM_X3, flops);
-    return check_launch("conv_stem_x3");
-  }
-  st = x3     ? (tile ? launch_tile_x3<MODE_FWD>(a, s, flops) : launch_gemm_x3<MODE_FWD>(a, s, flops))
-       : ws   ? launch_tile_ws<MODE_FWD>(a, s, flops)
-       : b16  ? launch_tile_b16<MODE_FWD>(a, s, flops)
-       : tile ? launch_tile_bf16<MODE_FWD>(a, s, flops)
-       : g16  ? launch_gemm_x3<MODE_FWD, 1>(a, s, flops)
-       : bf16 ? launch_gemm_bf16<MODE_FWD>(a, s, flops)
-              : launch_gemm<MODE_FWD>(a, s, flops);
-  return st;
+  if (f != Fam::stem) return launch_family<MODE_FWD>(f, a, s, flops);
+  const int64_t tiles = (int64_t)d->n * cdiv(d->ho, ST_TH) * cdiv(d->wo, ST_TW);
+  OF_CHECK_ARG(tiles < INT32_MAX, "conv stem: too many tiles");
+  // persistent (of_set_tuning key 31 = workgroups per CU, default as many as the LDS holds:
+  // 2 fp32 / 3 bf16 / 1 for the 64-channel form; 0: one tile per workgroup, the round-2..4
+  // grid): B staged once per workgroup, the next tile's halo loaded during this tile's MFMAs
+  const int groups = bf16 || g_stem_x3 != 2 ? 2 : 1;
+  const int per_cu = g_stem_persist < 0 ? (bf16 ? 3 : g_stem_x3 == 2 ? 1 : 2) : g_stem_persist;
+  const int64_t cap = per_cu > 0 ? (int64_t)per_cu * device_cus() : tiles * groups;
+  const unsigned grid = (unsigned)(std::min(tiles * groups, cap) / groups * groups);
+  // (conv_stem_x3 takes the tile count too: its own call, the same record)
+  const StemLaunch l = bf16 ? stem_rec<32, 1>() : g_stem_x3 == 2 ? stem_rec<64>() : stem_rec<32>();
+  if (timing_on()) timing_begin(s);
+  hipLaunchKernelGGL(l.fn, dim3(grid), dim3(l.threads), 0, s, a, (int)tiles);
+  if (timing_on()) timing_end(s, l.kind, flops);
+  return check_launch("conv_stem_x3");
 }
 
 int of_conv2d_fwd(const of_conv_desc* d, const float* x, int ldx, const float* w_fwd,
@@ -5854,27 +5986,22 @@ static int conv_dgrad_impl(int prec, const of_conv_desc* d, const float* dy, int
   OF_CHECK_ARG(((uintptr_t)dy & 15) == 0 && ((uintptr_t)w_bwd & 15) == 0,
                "conv dgrad: dy / w must be 16-byte aligned");
   OF_CHECK_ARG(d->stride == 1 || d->stride == 2, "conv dgrad: stride must be 1 or 2");
-  if (!prec && narrow_ok(d)) {
+  const Fam f = dgrad_family(d, prec, bnp != nullptr);
+  if (f == Fam::narrow) {
     OF_CHECK_ARG(!add && !act_post, "conv dgrad: the Cout <= 4 kernels take no added gradient");
     hipStream_t s = as_stream(stream);
     if (timing_on()) timing_begin(s);
     st = narrow_dgrad(d, dy, lddy, static_cast<const float*>(w_bwd), act_src, ld_act, act,
                       alpha, dx, lddx, s);
-    if (timing_on()) timing_end(s, MODE_DGRAD * 8 + KIND_NARROW, conv_flops(d));
+    if (timing_on()) timing_end(s, kind(KIND_F32, MODE_DGRAD, KIND_NARROW), conv_flops(d));
     return st;
   }
-  const bool tile = (bf16 || x3) && tile_ok(d);
+  const bool tile = prec && tile_ok(d);
   const bool in_place = add && add == dx && ld_add == lddx;
-  const bool ws = tile && bf16 && ws_ok(d, MODE_DGRAD);
-  // (bf16 with BN partial sums and key 32: conv_tile_b16, the split body with one plane)
-  const bool b16 = tile && bf16 && !ws && (g_tile_b16 == 1 || (bnp && g_bnp_b16));
-  GemmArgs a = tile ? tile_args(d, g, MODE_DGRAD, x3, b16, ws)
-                    : dgrad_args(d, g, bf16 || x3, in_place);
-  const bool g16 = bf16 && !tile && (g_gemm_b16 & 2);       // conv_gemm_x3<..., 1>
-  if ((x3 || g16) && !tile) gemm_x3_plan(a);
+  GemmArgs a = plan_args(d, g, MODE_DGRAD, f, in_place);
   if (a.tiles_total == 0)                                // every output already final
     return bnp ? fail(OF_EUNSUPPORTED, "conv dgrad bnp: no GEMM tiles") : OF_OK;
-  attach_slab(a, workspace, ws_bytes, tile ? 1 : (bf16 || x3) ? BKH : BK);
+  attach_slab(a, workspace, ws_bytes, tile ? 1 : prec ? BKH : BK);
   a.A = dy;
   a.lda = lddy;
   a.a_bytes = (int64_t)d->n * d->ho * d->wo * lddy * 4;
@@ -5895,9 +6022,9 @@ static int conv_dgrad_impl(int prec, const of_conv_desc* d, const float* dy, int
   hipStream_t s = as_stream(stream);
   const double flops = 2.0 * d->n * d->ho * d->wo * (double)d->cout * g.taps * d->cin;
   a.vec_ep = vec_ep_ok(a);
-  if (g_abl_noact && x3 && tile && !bnp) a.act_src = nullptr;   // key 39: timing ablation
+  if (g_abl_noact && f == Fam::tile_x3 && !bnp) a.act_src = nullptr;   // key 39: timing ablation
   // split 3x3 input gradient, one K slice: the direct epilogue (conv_dev.h direct_dgrad_f32)
-  a.direct16 = x3 && tile && (g_x3_direct & 2) && a.splits == 1 && a.vec_ep;
+  a.direct16 = f == Fam::tile_x3 && (g_x3_direct & 2) && a.splits == 1 && a.vec_ep;
   if (bnp) {
     // the BN partial sums ride on conv_tile_x3's vectorised one-slice epilogue only; any other
     // form: OF_EUNSUPPORTED before anything is launched (the caller runs the separate pass)
@@ -5907,8 +6034,9 @@ static int conv_dgrad_impl(int prec, const of_conv_desc* d, const float* dy, int
     // bf16 GEMM form measured 1780 -> 1726 pairs/s on the bf16 B = 32 step: declined)
     int64_t rows = 0;
     for (int gq = 0; gq < a.ngroups; ++gq) rows += a.grp[gq].M;
-    const bool form = tile ? (x3 || b16 ? X3_EPB == 1 : bf16 && !ws && EPC_BATCH)
-                           : x3 && EPC_BATCH && rows == (int64_t)d->n * d->h * d->w;
+    const bool form = f == Fam::tile_x3 || f == Fam::tile_b16 ? X3_EPB == 1
+                      : f == Fam::tile_bf16 ? (bool)EPC_BATCH
+                      : f == Fam::gemm_x3 && EPC_BATCH && rows == (int64_t)d->n * d->h * d->w;
     if (!(form && a.splits == 1 && a.vec_ep && act_src) ||
         a.N % 4 || ((uintptr_t)bnp->gamma & 15) || ((uintptr_t)bnp->beta & 15) ||
         ((uintptr_t)bnp->part & 15) || (bnp->res && (((uintptr_t)bnp->res & 15) || bnp->ld_res % 4)))
@@ -5923,15 +6051,7 @@ static int conv_dgrad_impl(int prec, const of_conv_desc* d, const float* dy, int
     a.bnp_b = bnp->beta;
     *bnp->nblk = (int)m_tiles;
   }
-  st = x3     ? (tile ? launch_tile_x3<MODE_DGRAD>(a, s, flops)
-                     : launch_gemm_x3<MODE_DGRAD>(a, s, flops))
-       : ws   ? launch_tile_ws<MODE_DGRAD>(a, s, flops)
-       : b16  ? launch_tile_b16<MODE_DGRAD>(a, s, flops)
-       : tile ? launch_tile_bf16<MODE_DGRAD>(a, s, flops)
-       : g16  ? launch_gemm_x3<MODE_DGRAD, 1>(a, s, flops)
-       : bf16 ? launch_gemm_bf16<MODE_DGRAD>(a, s, flops)
-              : launch_gemm<MODE_DGRAD>(a, s, flops);
-  return st;
+  return launch_family<MODE_DGRAD>(f, a, s, flops);
 }
 
 int of_conv2d_dgrad(const of_conv_desc* d, const float* dy, int lddy, const float* w_bwd,
@@ -5977,18 +6097,12 @@ int of_conv_pack_weights_x3(const of_conv_desc* d, const float* w_hwio, void* w3
 
 size_t of_conv2d_fwd_x3_workspace(const of_conv_desc* d) {
   if (validate(d) != OF_OK || narrow_ok(d)) return 0;
-  if (tile_ok(d)) return fd_workspace(tile_args(d, geo(d), MODE_FWD, true));
-  GemmArgs a = fwd_args(d, geo(d), true);
-  gemm_x3_plan(a);
-  return fd_workspace(a);
+  return fd_workspace(plan_args(d, geo(d), MODE_FWD, fwd_family(d, 2, false, false)));
 }
 
 size_t of_conv2d_dgrad_x3_workspace(const of_conv_desc* d) {
   if (validate(d) != OF_OK || narrow_ok(d)) return 0;
-  if (tile_ok(d)) return fd_workspace(tile_args(d, geo(d), MODE_DGRAD, true));
-  GemmArgs a = dgrad_args(d, geo(d), true);
-  gemm_x3_plan(a);
-  return fd_workspace(a);
+  return fd_workspace(plan_args(d, geo(d), MODE_DGRAD, dgrad_family(d, 2)));
 }
 
 int of_conv2d_fwd_x3(const of_conv_desc* d, const float* x, int ldx, const void* w3_fwd,
@@ -6015,26 +6129,9 @@ int of_conv2d_dgrad_add_x3(const of_conv_desc* d, const float* dy, int lddy,
                          dx, lddx, workspace, ws_bytes, stream);
 }
 
-size_t of_conv2d_wgrad_workspace(const of_conv_desc* d) {
-  if (validate(d) != OF_OK) return 0;
-  if (narrow_ok(d)) return narrow_wgrad_ws(d);
-  WgradPlan p = wgrad_plan(d);
-  return (size_t)p.splits * p.split_stride * sizeof(float);
-}
-
-size_t of_conv2d_wgrad_bf16_workspace(const of_conv_desc* d) {
-  if (validate(d) != OF_OK) return 0;
-  if (narrow_ok(d)) return narrow_wgrad_ws(d);
-  WgradPlan p = wgrad_plan(d, true);
-  return (size_t)p.splits * p.split_stride * sizeof(float);
-}
-
-size_t of_conv2d_wgrad_x3_workspace(const of_conv_desc* d) {
-  if (validate(d) != OF_OK) return 0;
-  if (narrow_ok(d)) return narrow_wgrad_ws(d);
-  WgradPlan p = wgrad_plan(d, false, wgx3_ok(d) || g_wgx3_gemm);
-  return (size_t)p.splits * p.split_stride * sizeof(float);
-}
+size_t of_conv2d_wgrad_workspace(const of_conv_desc* d) { return wgrad_workspace(d, 0); }
+size_t of_conv2d_wgrad_bf16_workspace(const of_conv_desc* d) { return wgrad_workspace(d, 1); }
+size_t of_conv2d_wgrad_x3_workspace(const of_conv_desc* d) { return wgrad_workspace(d, 2); }
 
 // prec: 0 fp32 MFMA, 1 bf16, 2 fp32 with conv_wgrad_tile_x3 where wgx3_ok (else as 0).
 static int conv_wgrad_impl(int prec, const of_conv_desc* d, const float* x, int ldx,
@@ -6045,25 +6142,22 @@ static int conv_wgrad_impl(int prec, const of_conv_desc* d, const float* x, int 
   int st = validate(d);
   if (st) return st;
   Geo g = geo(d);
-  const bool bf16 = prec == 1, x3 = prec == 2 && wgx3_ok(d);
-  const bool b16 = bf16 && g_wgrad_b16 && wgx3_ok(d);   // conv_wgrad_tile_b16
-  const bool x3g = prec == 2 && !x3 && g_wgx3_gemm;   // conv_wgrad_x3 (other shapes)
-  const bool g16 = bf16 && gemm_b16_wg(d);             // conv_wgrad_x3<..., 1>
+  const WFam f = wgrad_family(d, prec);
   OF_CHECK_ARG(x && dy && dw && workspace, "conv wgrad: NULL pointer");
   OF_CHECK_ARG(ldx >= d->cin_p && ldx % 4 == 0, "conv wgrad: ldx");
   OF_CHECK_ARG(lddy >= g.cout_p && lddy % 4 == 0, "conv wgrad: lddy");
   OF_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0,
                "conv wgrad: x / dy must be 16-byte aligned");
-  if (narrow_ok(d)) {
+  if (f == WFam::narrow) {
     OF_CHECK_ARG(!bn_g, "conv wgrad: the Cout <= 4 kernels take no BN scale");
     OF_CHECK_ARG(ws_bytes >= narrow_wgrad_ws(d), "conv wgrad: workspace too small");
     hipStream_t s = as_stream(stream);
     if (timing_on()) timing_begin(s);
     st = narrow_wgrad(d, x, ldx, dy, lddy, dw, db, accumulate, workspace, s);
-    if (timing_on()) timing_end(s, MODE_WGRAD * 8 + KIND_NARROW, conv_flops(d));
+    if (timing_on()) timing_end(s, kind(KIND_F32, MODE_WGRAD, KIND_NARROW), conv_flops(d));
     return st;
   }
-  WgradPlan p = wgrad_plan(d, bf16, x3 || x3g);
+  WgradPlan p = wgrad_plan(d, prec);
   OF_CHECK_ARG(ws_bytes >= (size_t)p.splits * p.split_stride * sizeof(float),
                "conv wgrad: workspace too small");
   GemmArgs a = base_args(d);
@@ -6090,134 +6184,34 @@ static int conv_wgrad_impl(int prec, const of_conv_desc* d, const float* x, int 
   a.vec_ep = vec_ep_ok(a);
   hipStream_t s = as_stream(stream);
   const double flops = 2.0 * a.K * (double)d->cout * g.taps * d->cin;
-  if (stem_wg_ok(d) && (!bf16 || g_stem_bf16)) {
-    a.K = stem_wg_tiles(d);
-    a.lda = ldx;
-    if (timing_on()) timing_begin(s);
-    if (bf16) hipLaunchKernelGGL(conv_wgrad_stem_x3<1>, dim3(a.splits), dim3(SW_NT), 0, s, a);
-    else hipLaunchKernelGGL(conv_wgrad_stem_x3<3>, dim3(a.splits), dim3(SW_NT), 0, s, a);
-    if (timing_on()) timing_end(s, bf16 ? 187 : 185, flops);     // bench.py KIND_STEM_*
-    st = check_launch("conv_wgrad_stem_x3");
-  } else if (b16) {
-    // the x3b configurations, all 9-tap: timing kinds 216 + cfg (bench.py X3_WGT 4 + cfg)
-    const int cfg = wgx3_cfg(d);
-    a.K = d->n * (int)cdiv(d->ho, wgx3_rows(cfg)) * (int)cdiv(d->wo, TT_W);
-    int cib, cob;
-    wgx3_blocks(d, cib, cob);
-    a.n_tiles = (int)cdiv(d->cout, cob);
-    a.tiles_total = (int)cdiv(g.cin_p, cib) * a.n_tiles;
-    dim3 grid(a.tiles_total * a.splits);
-    if (timing_on()) timing_begin(s);
-    if (g_wgx3b_stage == 0) {   // three shifted halo copies
-      if (cfg == 4) hipLaunchKernelGGL((conv_wgrad_tile_b16_c3<2, 2, 8>), grid, dim3(256), 0, s, a);
-      else if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_b16_c3<2, 4, 8>), grid, dim3(512), 0, s, a);
-      else if (cfg == 1) hipLaunchKernelGGL((conv_wgrad_tile_b16_c3<2, 3, 8>), grid, dim3(384), 0, s, a);
-      else if (cfg == 2) hipLaunchKernelGGL((conv_wgrad_tile_b16_c3<4, 2, 4>), grid, dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((conv_wgrad_tile_b16_c3<4, 1, 4>), grid, dim3(256), 0, s, a);
-    } else if (cfg == 4) hipLaunchKernelGGL((conv_wgrad_tile_b16<2, 2, 8>), grid, dim3(256), 0, s, a);
-    else if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_b16<2, 4, 8>), grid, dim3(512), 0, s, a);
-    else if (cfg == 1) hipLaunchKernelGGL((conv_wgrad_tile_b16<2, 3, 8>), grid, dim3(384), 0, s, a);
-    else if (cfg == 2) hipLaunchKernelGGL((conv_wgrad_tile_b16<4, 2, 4>), grid, dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((conv_wgrad_tile_b16<4, 1, 4>), grid, dim3(256), 0, s, a);
-    if (timing_on()) timing_end(s, 216 + cfg, flops);
-    st = check_launch("conv_wgrad_tile_b16");
-  } else if (x3) {
-    a.K = d->n * (int)cdiv(d->ho, wgx3_rows(wgx3_cfg(d))) * (int)cdiv(d->wo, TT_W);
-    int cib, cob;
-    wgx3_blocks(d, cib, cob);
-    const int cfg = wgx3_cfg(d);
-    a.n_tiles = (int)cdiv(d->cout, cob);
-    a.tiles_total = (int)cdiv(g.cin_p, cib) * a.n_tiles;
-    dim3 grid(a.tiles_total * a.splits);
-    if (timing_on()) timing_begin(s);
-    const bool x3b = g_wgx3b == 2 || (g_wgx3b == 1 && cfg == 0) || cfg == 4;
-    if (x3b) {
-      if (g_wgx3b_stage == 0 && g_wgx3b_mi == 2) {   // three shifted halo copies
-        if (cfg == 4) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<1, 4, 8, 2>), grid, dim3(256), 0, s, a);
-        else if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<1, 8, 8, 2>), grid, dim3(512), 0, s, a);
-        else if (cfg == 1) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<1, 6, 8, 2>), grid, dim3(384), 0, s, a);
-        else if (cfg == 2) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<2, 4, 4, 2>), grid, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<2, 2, 4, 2>), grid, dim3(256), 0, s, a);
-      } else if (g_wgx3b_stage == 0) {
-        if (cfg == 4) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<2, 2, 8>), grid, dim3(256), 0, s, a);
-        else if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<2, 4, 8>), grid, dim3(512), 0, s, a);
-        else if (cfg == 1) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<2, 3, 8>), grid, dim3(384), 0, s, a);
-        else if (cfg == 2) hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<4, 2, 4>), grid, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((conv_wgrad_tile_x3b_c3<4, 1, 4>), grid, dim3(256), 0, s, a);
-      } else if (g_wgx3b_mi == 2) {   // waves of 32 ci x 16 co
-        if (cfg == 4) hipLaunchKernelGGL((conv_wgrad_tile_x3b<1, 4, 8, 2>), grid, dim3(256), 0, s, a);
-        else if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_x3b<1, 8, 8, 2>), grid, dim3(512), 0, s, a);
-        else if (cfg == 1) hipLaunchKernelGGL((conv_wgrad_tile_x3b<1, 6, 8, 2>), grid, dim3(384), 0, s, a);
-        else if (cfg == 2) hipLaunchKernelGGL((conv_wgrad_tile_x3b<2, 4, 4, 2>), grid, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((conv_wgrad_tile_x3b<2, 2, 4, 2>), grid, dim3(256), 0, s, a);
-      } else if (cfg == 4) hipLaunchKernelGGL((conv_wgrad_tile_x3b<2, 2, 8>), grid, dim3(256), 0, s, a);
-      else if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_x3b<2, 4, 8>), grid, dim3(512), 0, s, a);
-      else if (cfg == 1) hipLaunchKernelGGL((conv_wgrad_tile_x3b<2, 3, 8>), grid, dim3(384), 0, s, a);
-      else if (cfg == 2) hipLaunchKernelGGL((conv_wgrad_tile_x3b<4, 2, 4>), grid, dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((conv_wgrad_tile_x3b<4, 1, 4>), grid, dim3(256), 0, s, a);
-    } else if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_x3<1, 4, 3, 8>), grid, dim3(768), 0, s, a);
-    else if (cfg == 1) hipLaunchKernelGGL((conv_wgrad_tile_x3<1, 3, 3, 8>), grid, dim3(576), 0, s, a);
-    else if (cfg == 2) hipLaunchKernelGGL((conv_wgrad_tile_x3<2, 2, 3, 4>), grid, dim3(768), 0, s, a);
-    else hipLaunchKernelGGL((conv_wgrad_tile_x3<2, 1, 3, 4>), grid, dim3(384), 0, s, a);
-    // timing kinds 144-147: the 3-tap form, 148-151: conv_wgrad_tile_x3b, 152: its cfg 4
-    // (bench.py X3_WGT)
-    if (timing_on()) timing_end(s, cfg == 4 ? 152 : 128 + MODE_WGRAD * 8 + cfg + (x3b ? 4 : 0), flops);
-    st = check_launch("conv_wgrad_tile_x3");
-  } else if (x3g) {
-    const int bn = d->cout > 64 ? 128 : 64;
-    a.n_tiles = (int)cdiv(d->cout, bn);
-    a.tiles_total = (int)cdiv(a.M, 128) * a.n_tiles;
-    dim3 grid(a.tiles_total * a.splits), block(512);
-    if (timing_on()) timing_begin(s);
-    if (bn == 128) hipLaunchKernelGGL((conv_wgrad_x3<128, 128, 4, 2>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_wgrad_x3<128, 64, 4, 2>), grid, block, 0, s, a);
-    if (timing_on()) timing_end(s, 160 + MODE_WGRAD * 8 + (bn == 128 ? 0 : 1), flops);
-    st = check_launch("conv_wgrad_x3");
-  } else if (g16) {
-    const int bn = d->cout > 64 ? 128 : 64;
-    a.n_tiles = (int)cdiv(d->cout, bn);
-    a.tiles_total = (int)cdiv(a.M, 128) * a.n_tiles;
-    dim3 grid(a.tiles_total * a.splits), block(512);
-    if (timing_on()) timing_begin(s);
-    if (bn == 128) hipLaunchKernelGGL((conv_wgrad_x3<128, 128, 4, 2, 1>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_wgrad_x3<128, 64, 4, 2, 1>), grid, block, 0, s, a);
-    if (timing_on()) timing_end(s, 240 + MODE_WGRAD * 8 + (bn == 128 ? 0 : 1), flops);
-    st = check_launch("conv_wgrad_x3_b16");
-  } else if (wgt_ok(d, bf16)) {
-    int cib, cob;
-    wgt_blocks(d, cib, cob);
-    a.K = d->n * (int)cdiv(d->ho, TT_H) * (int)cdiv(d->wo, TT_W);
-    a.n_tiles = (int)cdiv(d->cout, cob);
-    a.tiles_total = (int)cdiv(g.cin_p, cib) * a.n_tiles;
-    const int cfg = wgt_cfg(d);
-    dim3 grid(a.tiles_total * a.splits), block(256);
-    if (timing_on()) timing_begin(s);
-    if (bf16 && !g_wgt_pf) {
-      if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_bf16<1, 4, 0>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((conv_wgrad_tile_bf16<2, 2, 0>), grid, block, 0, s, a);
-    } else if (bf16) {
-      if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_bf16<1, 4>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((conv_wgrad_tile_bf16<2, 2>), grid, block, 0, s, a);
-    } else {
-      if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_tile_f32<1, 4>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((conv_wgrad_tile_f32<2, 2>), grid, block, 0, s, a);
-    }
-    if (timing_on()) timing_end(s, (bf16 ? 96 : 32) + MODE_WGRAD * 8 + cfg, flops);
-    st = check_launch("conv_wgrad_tile");
-  } else if (bf16) {
-    const int bn = pick_bn(a.N);
-    const int cfg = bn == 128 ? 0 : bn == 96 ? 1 : bn == 64 ? 2 : 3;
-    dim3 grid(a.tiles_total * a.splits), block(256);
-    if (timing_on()) timing_begin(s);
-    if (cfg == 0) hipLaunchKernelGGL((conv_wgrad_bf16<128, 128, 2, 2>), grid, block, 0, s, a);
-    else if (cfg == 1) hipLaunchKernelGGL((conv_wgrad_bf16<128, 96, 4, 1>), grid, block, 0, s, a);
-    else if (cfg == 2) hipLaunchKernelGGL((conv_wgrad_bf16<256, 64, 4, 1>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_wgrad_bf16<256, 32, 4, 1>), grid, block, 0, s, a);
-    if (timing_on()) timing_end(s, 64 + MODE_WGRAD * 8 + cfg, flops);
-    st = check_launch("conv_wgrad_bf16");
-  } else {
-    st = launch_gemm<MODE_WGRAD>(a, s, flops);
+  // each family's K unit and tile grid, then its instance
+  Launch l{};
+  unsigned grid = 0;   // (0: the tile grid)
+  switch (f) {
+    case WFam::stem:
+      a.K = stem_wg_tiles(d);
+      l = prec == 1 ? wgrad_stem_rec<1>() : wgrad_stem_rec<3>();
+      grid = a.splits;
+      break;
+    case WFam::tile_b16:
+    case WFam::tile_x3:
+      wgrad_tiles(a, d, g, true);
+      l = f == WFam::tile_b16 ? wgrad_tile_b16_launch(wgx3_cfg(d)) : wgrad_tile_x3_launch(wgx3_cfg(d));
+      break;
+    case WFam::gemm_x3:
+    case WFam::gemm_b16:
+      a.n_tiles = (int)cdiv(d->cout, d->cout > 64 ? 128 : 64);
+      a.tiles_total = (int)cdiv(a.M, 128) * a.n_tiles;
+      l = f == WFam::gemm_b16 ? wgrad_x3_launch<1>(d) : wgrad_x3_launch<3>(d);
+      break;
+    case WFam::tile:
+      wgrad_tiles(a, d, g, false);
+      l = wgrad_tile_launch(wgt_cfg(d), prec == 1);
+      break;
+    case WFam::gemm_bf16: l = wgrad_bf16_launch(a); break;
+    default: l = gemm_f32_launch<MODE_WGRAD>(a); break;
   }
+  st = launch<MODE_WGRAD>(l, a, s, flops, grid);
   if (st) return st;
   launch_wgrad_reduce(s, static_cast<const float*>(workspace), p.splits, p.split_stride, g.taps,
                       g.cin_p, d->cin, d->cout, p.ldc, dw, db, accumulate, bn_g, bn_v, bn_eps);
@@ -6232,7 +6226,7 @@ static bool stem_fused_ok(const of_conv_desc* d, int prec) {
 
 size_t of_stem_bwd_fused_workspace(const of_conv_desc* d, int precision) {
   if (validate(d) != OF_OK || !stem_fused_ok(d, precision)) return 0;
-  WgradPlan p = wgrad_plan(d, precision == 1, true);
+  WgradPlan p = wgrad_plan(d, precision);
   return (size_t)p.splits * (p.M + 2) * p.ldc * sizeof(float);
 }
 
@@ -6248,7 +6242,7 @@ int of_stem_bwd_fused(const of_conv_desc* d, int precision, const float* x, int 
                                  "kernels with an even output");
   OF_CHECK_ARG(x && dyp && y && gamma && beta && var && dw && workspace, "stem bwd fused: NULL");
   OF_CHECK_ARG(ldx >= d->cin_p && ldx % 4 == 0, "stem bwd fused: ldx");
-  WgradPlan p = wgrad_plan(d, precision == 1, true);
+  WgradPlan p = wgrad_plan(d, precision);
   const int64_t stride = (int64_t)(p.M + 2) * p.ldc;
   OF_CHECK_ARG(ws_bytes >= (size_t)p.splits * stride * sizeof(float),
                "stem bwd fused: workspace too small");
@@ -6280,11 +6274,8 @@ int of_stem_bwd_fused(const of_conv_desc* d, int precision, const float* x, int 
   a.st_y = y;
   hipStream_t s = as_stream(stream);
   const double flops = 2.0 * (double)d->n * d->ho * d->wo * d->cout * 49 * d->cin;
-  if (timing_on()) timing_begin(s);
-  if (precision == 1) hipLaunchKernelGGL((conv_wgrad_stem_x3<1, true>), dim3(a.splits), dim3(SW_NT), 0, s, a);
-  else hipLaunchKernelGGL((conv_wgrad_stem_x3<3, true>), dim3(a.splits), dim3(SW_NT), 0, s, a);
-  if (timing_on()) timing_end(s, precision == 1 ? 187 : 185, flops);   // bench.py KIND_STEM_*
-  st = check_launch("conv_wgrad_stem_x3 fused");
+  st = launch<MODE_WGRAD>(precision == 1 ? wgrad_stem_rec<1, true>() : wgrad_stem_rec<3, true>(),
+                          a, s, flops, a.splits);
   if (st) return st;
   Geo gg = geo(d);
   launch_wgrad_reduce(s, static_cast<const float*>(workspace), p.splits, stride, gg.taps,
@@ -6359,8 +6350,7 @@ int of_conv_pack_table_bn(int nconv, const of_conv_desc* descs, const float* con
 }
 
 size_t of_conv2d_wgrad_bn_workspace(const of_conv_desc* d, int precision) {
-  return precision == 1 ? of_conv2d_wgrad_bf16_workspace(d)
-         : precision == 2 ? of_conv2d_wgrad_x3_workspace(d) : of_conv2d_wgrad_workspace(d);
+  return wgrad_workspace(d, precision == 1 || precision == 2 ? precision : 0);
 }
 
 int of_conv2d_wgrad_bn(const of_conv_desc* d, int precision, const float* x, int ldx,
@@ -6389,13 +6379,8 @@ size_t of_conv2d_dgrad_bnp_bytes(const of_conv_desc* d) {
   Geo g = geo(d);
   size_t bytes = 0;
   for (int f = 0; f < 3; ++f) {   // conv_tile_x3, conv_tile_b16, conv_tile_bf16 / the GEMM
-    GemmArgs a;
-    if (tile_ok(d)) {
-      a = tile_args(d, g, MODE_DGRAD, f == 0, f == 1);
-    } else {
-      a = dgrad_args(d, g, true, f == 1);
-      gemm_x3_plan(a);
-    }
+    const Fam tiles[3] = {Fam::tile_x3, Fam::tile_b16, Fam::tile_bf16};
+    const GemmArgs a = plan_args(d, g, MODE_DGRAD, tile_ok(d) ? tiles[f] : Fam::gemm_x3, f == 1);
     if (a.n_tiles > 0) bytes = std::max(bytes, (size_t)(a.tiles_total / a.n_tiles) * 2 * a.N * 4);
   }
   return bytes;

@@ -396,17 +396,16 @@ __global__ __launch_bounds__(64 * (CWM * CWN + 4), 1) void conv_tile_ws(GemmArgs
 }
 
 // Kernel launch only (timing and the split-K epilogue stay with the caller).
-int launch_tile_ws_kernel(const GemmArgs& a, int mode, hipStream_t s) {
-  dim3 grid(a.tiles_total * a.splits), block(512);
-  const bool b128 = a.N > 96;
-  if (mode == MODE_FWD) {
-    if (b128) hipLaunchKernelGGL((conv_tile_ws<128, 8, 2, 2, MODE_FWD>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_tile_ws<96, 8, 2, 2, MODE_FWD>), grid, block, 0, s, a);
-  } else {
-    if (b128) hipLaunchKernelGGL((conv_tile_ws<128, 8, 2, 2, MODE_DGRAD>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_tile_ws<96, 8, 2, 2, MODE_DGRAD>), grid, block, 0, s, a);
-  }
-  return check_launch("conv_tile_ws");
+// threads: the expression of conv_tile_ws's __launch_bounds__; kind: cfg 0 (BN 128) or 1 (BN 96)
+template <int BN, int TH, int CWM, int CWN, int MODE>
+constexpr Launch tile_ws_rec() {
+  return {conv_tile_ws<BN, TH, CWM, CWN, MODE>, 64 * (CWM * CWN + 4), BN == 128 ? 0 : 1, "conv_tile_ws"};
+}
+Launch tile_ws_launch(const GemmArgs& a, int mode) {
+  static const Launch T[2][2] = {
+      {tile_ws_rec<128, 8, 2, 2, MODE_FWD>(), tile_ws_rec<96, 8, 2, 2, MODE_FWD>()},
+      {tile_ws_rec<128, 8, 2, 2, MODE_DGRAD>(), tile_ws_rec<96, 8, 2, 2, MODE_DGRAD>()}};
+  return T[mode != MODE_FWD][a.N > 96 ? 0 : 1];
 }
 
 }  // namespace oflow

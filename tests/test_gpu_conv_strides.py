@@ -171,6 +171,160 @@ class _Timing:
         return False
 
 
+# ------------------------------------------------------- which kernel a call selects ----
+# Timing kinds (bench.py kind_parts) of one forward, input-gradient and weight-gradient call
+# through the layer's own entry points, recorded before the host dispatch was rewritten as
+# tables.  (n, h, w, cin, cout, k, stride), precision -> (fwd, dgrad, wgrad); None: not run.
+DISPATCH_KINDS = {
+    # (a) 3x3 stride 1 by N tile: conv_tile_x3 / conv_tile_bf16 BN 32 / 64 / 96 / 128 (at this
+    # size key 27 gives the Cout 128 forward BN 64 tiles), weight-gradient configs 3 / 4 / 1 / 0
+    # (Cout 64 from 32 input channels is config 4; from 64 it is config 2)
+    ((1, 8, 32, 32, 32, 3, 1), "x3"): (131, 139, 147),
+    ((1, 8, 32, 32, 32, 3, 1), "bf16"): (99, 107, 114),
+    ((1, 8, 32, 32, 64, 3, 1), "x3"): (130, 139, 152),
+    ((1, 8, 32, 64, 64, 3, 1), "x3"): (None, None, 146),
+    ((1, 8, 32, 32, 64, 3, 1), "bf16"): (98, 107, 114),
+    ((1, 8, 32, 32, 96, 3, 1), "x3"): (129, 139, 145),
+    ((1, 8, 32, 32, 96, 3, 1), "bf16"): (97, 107, 112),
+    ((1, 8, 32, 32, 128, 3, 1), "x3"): (130, 139, 148),
+    ((1, 8, 32, 32, 128, 3, 1), "bf16"): (96, 107, 112),
+    # (b) Cout 64 with Cin % 64 != 0: the 32 x 64 channel blocks, 9-tap form
+    ((1, 8, 32, 96, 64, 3, 1), "x3"): (None, None, 152),
+    # (c) the 8 x 32 output tiles need >= 4 workgroups per CU (x3_tall): "tall" / "flat" below
+    ((8, 128, 256, 32, 128, 3, 1), "x3"): ({"tall": 128, "flat": 132}, None, None),
+    ((8, 128, 256, 32, 128, 3, 1), "bf16"): ({"tall": 100, "flat": 96}, None, None),
+    ((8, 16, 96, 128, 128, 3, 1), "x3"): (130, None, None),
+    ((8, 16, 96, 128, 128, 3, 1), "bf16"): (96, None, None),
+    # 1200 tiles of 4 x 32, unsplit: the single-buffered 4-wave BN 128 form
+    ((2, 160, 480, 16, 128, 3, 1), "x3"): (132, None, None),
+    # (d) stride 2: conv_gemm_x3 / conv_wgrad_x3 with three planes or one (key 16 = 6: bf16
+    # forward on conv_gemm_bf16)
+    ((1, 16, 16, 64, 128, 3, 2), "x3"): (160, 169, 176),
+    ((1, 16, 16, 64, 128, 3, 2), "bf16"): (64, 249, 256),
+    ((1, 16, 16, 64, 128, 1, 2), "x3"): (160, 169, 176),
+    ((1, 16, 16, 64, 128, 1, 2), "bf16"): (64, 249, 256),
+    ((1, 16, 16, 64, 64, 3, 2), "x3"): (161, 169, 177),
+    ((1, 16, 16, 64, 64, 3, 2), "bf16"): (66, 249, 257),
+    ((1, 16, 16, 64, 64, 1, 2), "x3"): (161, 169, 177),
+    ((1, 16, 16, 64, 64, 1, 2), "bf16"): (66, 249, 257),
+    # (e) the stem
+    ((1, 32, 32, 3, 64, 7, 2), "x3"): (184, None, 185),
+    ((1, 32, 32, 3, 64, 7, 2), "bf16"): (186, None, 187),
+    # (f) Cout <= 4: the VALU kernels
+    ((1, 8, 8, 32, 2, 3, 1), "f32"): (7, 15, 23),
+}
+# (g) one tuning key at a time on (a)'s Cout 128 layer: {precision: (fwd, dgrad, wgrad)}
+DISPATCH_TUNED_SHAPE = (1, 8, 32, 32, 128, 3, 1)
+DISPATCH_TUNED = {
+    (40, 0): {"x3": (130, 139, 148), "bf16": (96, 107, 112)},
+    (5, 2): {"x3": (130, 139, 148), "bf16": (96, 107, 112)},
+    (4, 0): {"x3": (130, 139, 144), "bf16": (96, 107, 112)},
+    (4, 2): {"x3": (130, 139, 148), "bf16": (96, 107, 112)},
+    (12, 1): {"x3": (130, 139, 148), "bf16": (198, 203, 112)},
+    (13, 1): {"x3": (130, 139, 148), "bf16": (96, 107, 216)},
+    (36, 2): {"x3": (135, 139, 148), "bf16": (96, 107, 112)},
+    (30, 0): {"x3": (130, 139, 148), "bf16": (96, 107, 112)},
+    (30, 1): {"x3": (130, 139, 148), "bf16": (96, 107, 112)},
+    (17, 0): {"x3": (130, 139, 148), "bf16": (96, 107, 112)},
+    (20, 0): {"x3": (130, 139, 148), "bf16": (96, 107, 112)},
+}
+DISPATCH_BITWISE = {40, 30, 17, 20}      # keys that pick a sibling instance: the same bits
+# key 30 picks among conv_gemm_x3 instances, which (a)'s layer never runs: (d)'s 3x3 too
+DISPATCH_RING_SHAPE = (1, 16, 16, 64, 128, 3, 2)
+
+
+def _dispatch_run(lib, shape, prec, passes=(0, 1, 2)):
+    """One contiguous call per pass; ([kind or None] * 3, [output or None] * 3)."""
+    from optical_flow_amd._lib import ACT_NONE, call
+    ops = _ops()
+    n, h, w, cin, cout, k, s = shape
+    cin_p, cout_p = _r4(cin), _r4(cout)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(zlib.crc32(repr(shape).encode()))
+    rnd = lambda *sh: torch.randn(*sh, device="cuda", generator=gen)
+    layer = ops.ConvLayer(rnd(k, k, cin, cout) * (2.0 / (k * k * cin)) ** 0.5, rnd(cout) * 0.1,
+                          stride=s, act=ACT_NONE, cin_p=cin_p,
+                          precision="bf16" if prec == "bf16" else "fp32", f32_split=prec == "x3")
+    d = layer.desc(n, h, w)
+    wf, wd = layer.packed(d)
+    x = torch.zeros(n, h, w, cin_p, device="cuda")
+    x[..., :cin] = rnd(n, h, w, cin)
+    dy = torch.zeros(n, d.ho, d.wo, cout_p, device="cuda")
+    dy[..., :cout] = rnd(n, d.ho, d.wo, cout)
+    P, st = ops._ptr, ops._stream()
+    kinds, outs = [None] * 3, [None] * 3
+    for m in passes:
+        ent, wsb = (layer.fwd_entry, layer.dgrad_entry, layer.wgrad_entry)[m](d)
+        ws = torch.empty(wsb // 4 + 4, device="cuda")
+        with _Timing(lib) as tm:
+            if m == 0:
+                out = torch.full((n, d.ho, d.wo, cout), SENTINEL, device="cuda")
+                call(ent, C.byref(d), P(x), cin_p, P(wf), P(layer.bias), None, None, None, None,
+                     1e-3, None, 0, ACT_NONE, ALPHA, None, 0, P(out), cout, P(ws), wsb, st)
+            elif m == 1:
+                out = torch.full((n, h, w, cin_p), SENTINEL, device="cuda")
+                call(ent, C.byref(d), P(dy), cout_p, P(wd), None, 0, ACT_NONE, ALPHA, P(out),
+                     cin_p, P(ws), wsb, st)
+            else:
+                out = torch.full((k, k, cin, cout), SENTINEL, device="cuda")
+                db = torch.full((cout,), SENTINEL, device="cuda")
+                call(ent, C.byref(d), P(x), cin_p, P(dy), cout_p, P(out), P(db), 0, P(ws), wsb, st)
+        assert len(tm.kinds) == 1, (shape, prec, m, tm.kinds)
+        kinds[m], outs[m] = tm.kinds.pop(), out
+    return kinds, outs
+
+
+def _dispatch_measure(lib):
+    """Everything test_dispatch_kinds compares: (kinds of DISPATCH_KINDS' calls, kinds per tuned
+    key, the keys of DISPATCH_BITWISE whose outputs differed from the default run's)."""
+    plain, tuned, differ = {}, {}, []
+    base = {}
+    for (shape, prec), want in DISPATCH_KINDS.items():
+        passes = [m for m in range(3) if want[m] is not None]
+        plain[shape, prec], outs = _dispatch_run(lib, shape, prec, passes)
+        if shape == DISPATCH_TUNED_SHAPE:
+            base[prec] = outs
+    base["ring"] = _dispatch_run(lib, DISPATCH_RING_SHAPE, "x3")
+    defaults = {40: 1, 5: 1, 4: 1, 12: 0, 13: 0, 36: 0, 30: 2, 17: 1, 20: 1}
+    try:
+        for (key, val) in DISPATCH_TUNED:
+            assert lib.of_set_tuning(key, val) == 0
+            tuned[key, val] = {}
+            for prec in ("x3", "bf16"):
+                tuned[key, val][prec], outs = _dispatch_run(lib, DISPATCH_TUNED_SHAPE, prec)
+                if key in DISPATCH_BITWISE and not all(map(torch.equal, outs, base[prec])):
+                    differ.append((key, val, prec))
+            if key == 30:
+                kinds, outs = _dispatch_run(lib, DISPATCH_RING_SHAPE, "x3")
+                if kinds != base["ring"][0] or not all(map(torch.equal, outs, base["ring"][1])):
+                    differ.append((key, val, "ring"))
+            assert lib.of_set_tuning(key, defaults[key]) == 0
+    finally:
+        for key, val in defaults.items():
+            lib.of_set_tuning(key, val)
+    return plain, tuned, differ
+
+
+def test_dispatch_kinds():
+    """The kernel each call selects (its timing kind), by shape, precision and tuning key,
+    against DISPATCH_KINDS / DISPATCH_TUNED; the sibling instances of keys 40, 30, 17 and 20
+    give the default run's bits."""
+    from optical_flow_amd import _lib
+    lib = _lib.lib()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    plain, tuned, differ = _dispatch_measure(lib)
+    for (shape, prec), want in DISPATCH_KINDS.items():
+        n, h, w = shape[:3]
+        # x3_tall (conv_f32.hip): 8 x 32 tiles while they leave >= 4 workgroups per CU
+        form = "tall" if n * -(-h // 8) * -(-w // 32) >= 4 * cus else "flat"
+        want = [q[form] if isinstance(q, dict) else q for q in want]
+        print("dispatch %s %s: %s" % ("x".join(map(str, shape)), prec, plain[shape, prec]))
+        assert plain[shape, prec] == want, (shape, prec, plain[shape, prec], want)
+    for setting, want in DISPATCH_TUNED.items():
+        print("dispatch key %d = %d: %s" % (setting + (tuned[setting],)))
+        assert tuned[setting] == {p: list(v) for p, v in want.items()}, (setting, tuned[setting])
+    assert not differ, differ
+
 # ------------------------------------------------------------------------- cases ----
 # ((n, h, w, cin, cout, k, stride), forward activation, precisions)
 CASES = [
