@@ -377,6 +377,37 @@ int of_flow_smooth_bwd_multi(const float* const* img6s, const float* const* flow
                              const float* dloss, float* const* dflows, const int* lds,
                              int accumulate, void* stream);
 
+/* Soft ternary census data term (illumination-robust), every level in one launch (levels <= 8;
+ * level l holds img6s[l] (n,hs[l],ws[l],6), of_pyramid6's output -- channels 0..2 image 1,
+ * 3..5 image 2 -- and flows[l] (n,hs[l],ws[l],2)).  With S = 255, c_t = 0.81, c_d = 0.1,
+ * r = radius in 1..3, K = (2r+1)^2 - 1,
+ *   g1[p] = S * mean_{c<3} img6[p,c],   u[p] = S * mean_{c<3} warp(img6[...,3:6], flow)[p,c]
+ *   (the photometric term's bilinear sampling),
+ *   tau(d) = d / sqrt(c_t + d*d),   phi(e) = e*e / (c_d + e*e),
+ *   e[p,o] = tau(g1[p+o] - g1[p]) - tau(u[p+o] - u[p])  for the window offsets o != 0 whose
+ *   p+o lies inside the same image (no pair crosses a row end or an image boundary),
+ *   C_l = (1/K) * sum_p sum_o phi(e[p,o]).
+ * Forward: one partial per 8 x 32 pixel tile, concatenated in level order (the partials-count
+ * function gives a level's share); level l's slice sums to coefs[l] * C_l and of_sum_partials
+ * reduces them.  When dcdfs is not NULL, dcdfs[l] (dense (n,hs[l],ws[l],2), 8-byte aligned)
+ * receives the unscaled d C_l / d flow; with dcdfs NULL only the value is computed.  The images
+ * are constants.  of_census_workspace_floats is the per-level scratch the forward wants in
+ * workspaces[l]; it is 0 in this build (the tile recomputes its halo) and workspaces may then
+ * be NULL.  Backward: dflows[l][p*lds[l] + c] (=|+=) coefs[l] * dloss[0] * dcdfs[l][p][c] for
+ * c < 2 (dloss NULL: 1; further channels of a padded row are not touched; accumulate != 0
+ * adds).  No atomics, no allocation, no host sync.  OF_EINVAL (and no launch) for levels
+ * outside 1..8, n, h or w < 1, radius outside 1..3, lds[l] < 2, NULL partials, a NULL workspace
+ * where the size function returns > 0. */
+int of_census_partials(int n, int h, int w);
+int of_census_workspace_floats(int n, int h, int w);
+int of_census_fwd_multi(const float* const* img6s, const float* const* flows, int n,
+                        const int* hs, const int* ws, int levels, int radius,
+                        const float* coefs, float* const* workspaces, float* const* dcdfs,
+                        float* partials, void* stream);
+int of_census_bwd_multi(const float* const* dcdfs, int n, const int* hs, const int* ws,
+                        int levels, const float* coefs, const float* dloss,
+                        float* const* dflows, const int* lds, int accumulate, void* stream);
+
 /* Keras Adam (train.py:34,56; P13), one launch over a flat parameter arena, g' = g*gscale
  * (gscale folds the 1/world of a data-parallel gradient average):
  * m += (g'-m)(1-b1); v += (g'^2-v)(1-b2); p -= lr_t * m / (sqrt(v) + eps). */

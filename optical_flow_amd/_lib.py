@@ -174,6 +174,12 @@ PROTOTYPES = {
     "of_flow_smooth_bwd_multi": (I, [C.POINTER(P), C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I,
                                      F, F, C.POINTER(F), C.POINTER(F), P, C.POINTER(P),
                                      C.POINTER(I), I, P]),
+    "of_census_partials": (I, [I, I, I]),
+    "of_census_workspace_floats": (I, [I, I, I]),
+    "of_census_fwd_multi": (I, [C.POINTER(P), C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I, I,
+                                C.POINTER(F), C.POINTER(P), C.POINTER(P), P, P]),
+    "of_census_bwd_multi": (I, [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I, C.POINTER(F), P,
+                                C.POINTER(P), C.POINTER(I), I, P]),
     "of_stem_bwd_fused_workspace": (SZ, [PD, I]),
     "of_stem_bwd_fused": (I, [PD, I, P, I, P, P, P, P, P, P, F, P, P, P, P, I, P, SZ, P]),
     # BatchNormalization in training mode (bn_mode="training")

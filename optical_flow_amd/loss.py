@@ -14,18 +14,37 @@ class LossLayer:
     that weight times the edge-aware first-order smoothness of every scale's flow: the mean
     Charbonnier penalty sqrt(d^2 + smoothness_eps) of the vertical plus that of the horizontal
     first differences, each weighted by exp(-edge_alpha * mean |d image1|) across the same
-    pixel pair, averaged over scales (ops.flow_loss; DESIGN.md has the definition)."""
+    pixel pair, averaged over scales (ops.flow_loss; DESIGN.md has the definition).
 
-    def __init__(self, smoothness_weight=0.0, edge_alpha=0.0, smoothness_eps=1e-4):
+    ``census_weight`` > 0 (build-added) adds that weight times the soft ternary census term,
+    an illumination-robust data term that compares the local intensity order of image 1 and
+    of the warped image 2 in a (2 census_radius + 1)^2 window, averaged over pixels and scales
+    (ops.census_loss; DESIGN.md "Census term").  ``photometric_weight`` scales the photometric
+    term; 0 drops it (its kernels are not launched), which needs ``census_weight`` > 0."""
+
+    def __init__(self, smoothness_weight=0.0, edge_alpha=0.0, smoothness_eps=1e-4,
+                 census_weight=0.0, census_radius=3, photometric_weight=1.0):
         if not smoothness_weight >= 0:
             raise ValueError("smoothness_weight must be >= 0, got %r" % (smoothness_weight,))
         if not edge_alpha >= 0:
             raise ValueError("edge_alpha must be >= 0, got %r" % (edge_alpha,))
         if not smoothness_eps > 0:
             raise ValueError("smoothness_eps must be > 0, got %r" % (smoothness_eps,))
+        if not census_weight >= 0:
+            raise ValueError("census_weight must be >= 0, got %r" % (census_weight,))
+        if not photometric_weight >= 0:
+            raise ValueError("photometric_weight must be >= 0, got %r" % (photometric_weight,))
+        if census_radius not in (1, 2, 3):
+            raise ValueError("census_radius must be 1, 2 or 3, got %r" % (census_radius,))
+        if census_weight == 0 and photometric_weight == 0:
+            raise ValueError("census_weight and photometric_weight are both 0: the loss needs "
+                             "a data term")
         self.smoothness_weight = float(smoothness_weight)
         self.edge_alpha = float(edge_alpha)
         self.smoothness_eps = float(smoothness_eps)
+        self.census_weight = float(census_weight)
+        self.census_radius = int(census_radius)
+        self.photometric_weight = float(photometric_weight)
 
     def __call__(self, batch_imgs, flows):
         num_scales = len(flows)
@@ -36,7 +55,12 @@ class LossLayer:
             assert flows[scale_idx].shape[1] == scaled_height
             assert flows[scale_idx].shape[2] == scaled_width
         assert batch_imgs.shape[3] == 6
-        if self.smoothness_weight == 0.0:
-            return ops.photometric_loss(batch_imgs, list(flows))
-        return ops.flow_loss(batch_imgs, list(flows), self.smoothness_weight, self.edge_alpha,
-                             self.smoothness_eps)
+        if self.census_weight == 0.0 and self.photometric_weight == 1.0:
+            if self.smoothness_weight == 0.0:
+                return ops.photometric_loss(batch_imgs, list(flows))
+            return ops.flow_loss(batch_imgs, list(flows), self.smoothness_weight,
+                                 self.edge_alpha, self.smoothness_eps)
+        return ops.census_flow_loss(batch_imgs, list(flows), self.census_weight,
+                                    self.census_radius, self.photometric_weight,
+                                    self.smoothness_weight, self.edge_alpha,
+                                    self.smoothness_eps)

@@ -2357,3 +2357,213 @@ def flow_loss(batch_imgs, flows, smoothness_weight, edge_alpha=0.0, eps=1e-4):
         fgs = [None] * len(flows)
     return _FlowLoss.apply(batch_imgs, fgs,
                            (float(smoothness_weight), float(edge_alpha), float(eps)), *flows)
+
+
+# ================================================================== census term =====
+def _census_coefs(n, hs, ws, scale):
+    """The normalisers of the census term, times ``scale``: the mean over each level's
+    pixels and over the levels (the 1/K of the window is in the kernel)."""
+    ns = len(hs)
+    return [scale / (ns * n * h * w) for h, w in zip(hs, ws)]
+
+
+def _census_fwd(pyr, fl, radius, coefs, want_grad):
+    """of_census_fwd_multi over every level: (partials, planes).  The partials sum to the
+    weighted term (the coefficients are applied in the kernel); planes[l] is the unscaled
+    d C_l / d flow that of_census_bwd_multi scales into d(flow), or None without want_grad."""
+    lib = _lib.lib()
+    ns = len(fl)
+    n = fl[0].shape[0]
+    hs = [f.shape[1] for f in fl]
+    ws_ = [f.shape[2] for f in fl]
+    parts = torch.empty(sum(lib.of_census_partials(n, h, w) for h, w in zip(hs, ws_)),
+                        device=fl[0].device)
+    planes = [torch.empty_like(f) for f in fl] if want_grad else None
+    wsf = [lib.of_census_workspace_floats(n, h, w) for h, w in zip(hs, ws_)]
+    wss = [torch.empty(k, device=fl[0].device) if k > 0 else None for k in wsf]
+    call("of_census_fwd_multi", _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
+         _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs), _arr(C.c_int, ws_),
+         ns, radius, _arr(C.c_float, coefs),
+         _arr(C.c_void_p, [t.data_ptr() if t is not None else None for t in wss])
+         if any(wsf) else None,
+         _arr(C.c_void_p, [p.data_ptr() for p in planes]) if planes is not None else None,
+         _ptr(parts), _stream())
+    return parts, planes
+
+
+def _census_bwd(planes, lv, coefs, dloss, accumulate):
+    """of_census_bwd_multi for the levels in ``lv`` ((level, output, row stride), as
+    _PhotoLoss.backward builds them)."""
+    m = len(lv)
+    n = planes[0].shape[0]
+    call("of_census_bwd_multi", _arr(C.c_void_p, [planes[k].data_ptr() for k, _, _ in lv]), n,
+         _arr(C.c_int, [planes[k].shape[1] for k, _, _ in lv]),
+         _arr(C.c_int, [planes[k].shape[2] for k, _, _ in lv]), m,
+         _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
+         _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
+         _arr(C.c_int, [ld for _, _, ld in lv]), accumulate, _stream())
+
+
+class _Census(torch.autograd.Function):
+    """The soft ternary census term of every level (include/oflow.h, of_census_fwd_multi):
+    mean over levels of C_l / (B h_l w_l).  The forward also leaves d C_l / d flow (the window
+    loop forms both); the backward scales it.  The images are constants."""
+
+    @staticmethod
+    def forward(ctx, batch_imgs, radius, *flows):
+        _check_dev(batch_imgs, *flows)
+        assert 1 <= len(flows) <= 8
+        fl = [f.contiguous() for f in flows]
+        n = fl[0].shape[0]
+        pyr = _pyramid6(batch_imgs.contiguous(), fl)
+        coefs = _census_coefs(n, [f.shape[1] for f in fl], [f.shape[2] for f in fl], 1.0)
+        parts, planes = _census_fwd(pyr, fl, radius, coefs, any(ctx.needs_input_grad[2:]))
+        out = torch.empty((), device=parts.device)
+        call("of_sum_partials", _arr(C.c_void_p, [parts.data_ptr()]),
+             _arr(C.c_int, [parts.numel()]), _arr(C.c_float, [1.0]), 1, _ptr(out), _stream())
+        ctx.save_for_backward(*(planes or []))
+        ctx.coefs = coefs
+        return out
+
+    @staticmethod
+    def backward(ctx, dloss):
+        planes = ctx.saved_tensors
+        dloss = dloss.contiguous()
+        grads, lv = [], []
+        for k in range(len(ctx.coefs)):
+            if not ctx.needs_input_grad[2 + k]:
+                grads.append(None)
+                continue
+            df = torch.empty_like(planes[k])
+            grads.append(df)
+            lv.append((k, df, 2))
+        if lv:
+            _census_bwd(planes, lv, ctx.coefs, dloss, 0)
+        return (None, None, *grads)
+
+
+def _census_radius(radius):
+    if radius not in (1, 2, 3):
+        raise ValueError("census radius must be 1, 2 or 3, got %r" % (radius,))
+    return int(radius)
+
+
+def census_loss(batch_imgs, flows, radius=3):
+    """The census term alone (a scalar; plain gradients for the flows)."""
+    return _Census.apply(batch_imgs, _census_radius(radius), *flows)
+
+
+class _CensusFlowLoss(torch.autograd.Function):
+    """photometric_weight * photometric + census_weight * census + smoothness_weight *
+    smoothness on one image pyramid; a term whose weight is 0 launches nothing.  One Function
+    for all terms because of the FlowGrad protocol (see _FlowLoss): in the backward the first
+    term present overwrites each level's d(flow) output and the later ones add into it."""
+
+    @staticmethod
+    def forward(ctx, batch_imgs, fgs, cfg, *flows):
+        pw, cw, radius, sw, edge_alpha, eps = cfg
+        _check_dev(batch_imgs, *flows)
+        assert pw != 0 or cw != 0, "a data term is needed: both data weights are 0"
+        ctx.fgs = fgs
+        b = batch_imgs.contiguous()
+        n = b.shape[0]
+        ns = len(flows)
+        if cw != 0 and sw != 0:
+            assert 1 <= ns <= 6, "of_sum_partials takes 8 groups: 6 levels, census, smoothness"
+        else:
+            assert 1 <= ns <= 7, "of_sum_partials takes 8 groups: 7 levels and one more term"
+        s = _stream()
+        fl = [f.contiguous() for f in flows]
+        pyr = _pyramid6(b, fl)
+        hs = [p.shape[1] for p in pyr]
+        ws_ = [p.shape[2] for p in pyr]
+        groups = []
+        keep = []                       # partial arrays stay alive until the sum is enqueued
+        coefs = [pw / (ns * n * h * w * 3) for h, w in zip(hs, ws_)]
+        if pw != 0:
+            nparts = [_lib.lib().of_photo_l1_partials(n, h, w) for h, w in zip(hs, ws_)]
+            parts = torch.empty(sum(nparts), device=b.device)
+            call("of_photo_l1_fwd_multi", _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
+                 _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs),
+                 _arr(C.c_int, ws_), ns, _ptr(parts), s)
+            off = 0
+            for k in range(ns):
+                groups.append((parts.data_ptr() + 4 * off, nparts[k], coefs[k]))
+                off += nparts[k]
+            keep.append(parts)
+        # the census and smoothness partials carry their coefficients: one group each
+        ccoefs = _census_coefs(n, hs, ws_, cw)
+        planes = None
+        if cw != 0:
+            cparts, planes = _census_fwd(pyr, fl, radius, ccoefs, any(ctx.needs_input_grad[3:]))
+            groups.append((cparts.data_ptr(), cparts.numel(), 1.0))
+            keep.append(cparts)
+        cv, ch = _smooth_coefs(n, hs, ws_, sw)
+        if sw != 0:
+            sparts = _smooth_fwd(pyr, fl, edge_alpha, eps, cv, ch)
+            groups.append((sparts.data_ptr(), sparts.numel(), 1.0))
+            keep.append(sparts)
+        loss = torch.empty((), device=b.device)
+        call("of_sum_partials", _arr(C.c_void_p, [g[0] for g in groups]),
+             _arr(C.c_int, [g[1] for g in groups]), _arr(C.c_float, [g[2] for g in groups]),
+             len(groups), _ptr(loss), s)
+        ctx.save_for_backward(*pyr, *fl, *(planes or []))
+        ctx.cfg = (ns, pw, cw, sw, edge_alpha, eps, coefs, ccoefs, cv, ch)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        ns, pw, cw, sw, edge_alpha, eps, coefs, ccoefs, cv, ch = ctx.cfg
+        saved = ctx.saved_tensors
+        pyr, flows, planes = saved[:ns], saved[ns:2 * ns], saved[2 * ns:]
+        dloss = dloss.contiguous()
+        s = _stream()
+        grads, lv = [], []          # lv: (level, output, row stride) of one multi launch
+        for k in range(ns):
+            if not ctx.needs_input_grad[3 + k]:
+                grads.append(None)
+                continue
+            fg = ctx.fgs[k]
+            if fg is not None:         # into the flow head's padded gradient (FlowGrad)
+                buf = fg.buffer()
+                fg.filled = True
+                grads.append(buf[..., :2])
+                lv.append((k, buf, 4))
+                continue
+            df = torch.empty_like(flows[k])
+            grads.append(df)
+            lv.append((k, df, 2))
+        if lv:
+            m = len(lv)
+            n = pyr[0].shape[0]
+            written = 0                # the first term present writes, the others add
+            if pw != 0:
+                call("of_photo_l1_bwd_multi",
+                     _arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]),
+                     _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]), n,
+                     _arr(C.c_int, [pyr[k].shape[1] for k, _, _ in lv]),
+                     _arr(C.c_int, [pyr[k].shape[2] for k, _, _ in lv]), m,
+                     _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
+                     _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
+                     _arr(C.c_int, [ld for _, _, ld in lv]), s)
+                written = 1
+            if cw != 0:
+                _census_bwd(planes, lv, ccoefs, dloss, written)
+                written = 1
+            if sw != 0:
+                _smooth_bwd(pyr, flows, lv, edge_alpha, eps, cv, ch, dloss, written)
+        return (None, None, None, *grads)
+
+
+def census_flow_loss(batch_imgs, flows, census_weight, census_radius=3, photometric_weight=1.0,
+                     smoothness_weight=0.0, edge_alpha=0.0, eps=1e-4):
+    """The training loss with the census data term: ``photometric_weight`` times
+    photometric_loss plus ``census_weight`` times census_loss plus ``smoothness_weight`` times
+    flow_smoothness, in one Function (see _CensusFlowLoss).  At least one data weight must be
+    non-zero; the kernels of a term whose weight is 0 are not launched."""
+    fgs = [getattr(f, "_of_flowgrad", None) for f in flows]
+    if any(fg is not None and fg.shape != tuple(f.shape) for fg, f in zip(fgs, flows)):
+        fgs = [None] * len(flows)
+    cfg = (float(photometric_weight), float(census_weight), _census_radius(census_radius),
+           float(smoothness_weight), float(edge_alpha), float(eps))
+    return _CensusFlowLoss.apply(batch_imgs, fgs, cfg, *flows)

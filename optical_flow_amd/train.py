@@ -276,6 +276,12 @@ def build_parser():
                     help="weight of the edge-aware flow smoothness term (0: the reference loss)")
     ap.add_argument("--edge-alpha", type=float, default=0.0,
                     help="edge sensitivity of the smoothness term (0: unweighted)")
+    ap.add_argument("--census-weight", type=float, default=0.0,
+                    help="weight of the soft ternary census data term (0: off)")
+    ap.add_argument("--census-radius", type=int, default=3, choices=(1, 2, 3),
+                    help="census window radius r, a (2r+1) x (2r+1) window")
+    ap.add_argument("--photometric-weight", type=float, default=1.0,
+                    help="weight of the photometric L1 term (0 with --census-weight: census only)")
     g = ap.add_argument_group(
         "augmentation (with --kitti only)", "seeded by --seed; both images of a pair get the "
         "same draw; an --aug-* flag without --augment starts from no augmentation")
@@ -311,18 +317,31 @@ def main(argv=None):
         ap.error("--augment / --aug-* apply only with --kitti: without it the driver trains on "
                  "synthetic pairs, which are not augmented")
 
+    try:
+        loss_layer = LossLayer(args.smoothness_weight, args.edge_alpha,
+                               census_weight=args.census_weight,
+                               census_radius=args.census_radius,
+                               photometric_weight=args.photometric_weight)
+    except ValueError as e:
+        ap.error(str(e))
+
     rank, world, local = init_from_env()
     torch.cuda.set_device(local)
     net = build_flow_net(args.height, args.width, args.pretrained, seed=args.seed)
     if rank == 0:
         net.summary()
     opt = KerasAdam(net.store, learning_rate=args.lr)
-    trainer = Trainer(net, opt, LossLayer(args.smoothness_weight, args.edge_alpha))
+    trainer = Trainer(net, opt, loss_layer)
     log = open(args.log, "a") if (args.log and rank == 0) else None
-    if log and (args.smoothness_weight or args.edge_alpha or augment is not None):
+    census = (args.census_weight != 0.0 or args.census_radius != 3 or
+              args.photometric_weight != 1.0)
+    if log and (args.smoothness_weight or args.edge_alpha or augment is not None or census):
         # header record (no "step" key); a default run's log holds step records only, as before
         head = {"header": True, "smoothness_weight": args.smoothness_weight,
                 "edge_alpha": args.edge_alpha}
+        if census:
+            head.update(census_weight=args.census_weight, census_radius=args.census_radius,
+                        photometric_weight=args.photometric_weight)
         if augment is not None:
             head["augment"] = augment.as_dict()
         log.write(json.dumps(head) + "\n")

@@ -2,6 +2,7 @@
 
 python tools/hip_trajectory.py --steps 26 [--det] [--precision fp32] --out gpurun_out/traj.jsonl
     [--smoothness-weight 0.2 --edge-alpha 10]      (the loss with the smoothness term on)
+    [--census-weight 1 --census-radius 3 --photometric-weight 1]    (with the census term on)
 
 Same weights, batch and optimizer as bench.py and tools/oracle_trajectory.py; one JSON line
 per step: loss and mean / max |flow| per level of that step's forward (the weights before the
@@ -33,6 +34,9 @@ def main():
     ap.add_argument("--oracle-every", type=int, default=0)
     ap.add_argument("--smoothness-weight", type=float, default=0.0)
     ap.add_argument("--edge-alpha", type=float, default=0.0)
+    ap.add_argument("--census-weight", type=float, default=0.0)
+    ap.add_argument("--census-radius", type=int, default=3)
+    ap.add_argument("--photometric-weight", type=float, default=1.0)
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     from optical_flow_amd import _lib, ops
@@ -47,7 +51,10 @@ def main():
     vals = init_params(flow_net_spec(levels=4), 0)
     net = FlowNet(H, W, values=vals, precision=args.precision)
     trainer = Trainer(net, KerasAdam(net.store),
-                      LossLayer(args.smoothness_weight, args.edge_alpha))
+                      LossLayer(args.smoothness_weight, args.edge_alpha,
+                                census_weight=args.census_weight,
+                                census_radius=args.census_radius,
+                                photometric_weight=args.photometric_weight))
     batch_np = synthetic_batch(B, H, W, seed=1234)
     batch = torch.from_numpy(batch_np).cuda()
     blocks = list(encoder_blocks(4))
@@ -57,6 +64,10 @@ def main():
             if args.smoothness_weight:
                 rec.update({"smoothness_weight": args.smoothness_weight,
                             "edge_alpha": args.edge_alpha})
+            if args.census_weight or args.photometric_weight != 1.0:
+                rec.update({"census_weight": args.census_weight,
+                            "census_radius": args.census_radius,
+                            "photometric_weight": args.photometric_weight})
             if args.oracle_every and s % args.oracle_every == 0:
                 from oracle import ref_flow as R
                 p = {k: v.detach().double().cpu() for k, v in net.store.params.items()}
