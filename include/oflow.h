@@ -421,6 +421,40 @@ int of_adam_keras_dev(float* p, const float* g, float* m, float* v, int64_t n, f
                       int32_t* iter, float beta1, float beta2, float eps, float gscale,
                       void* stream);
 
+/* Global-norm gradient clipping (tf.keras Adam's global_clipnorm, tf.clip_by_global_norm over
+ * every gradient) and the non-finite update guard, all on the device.
+ *
+ * of_grad_sumsq: partials[b], b < P = of_grad_sumsq_partials(n), = the sum of g[i]^2 over
+ * workgroup b's range, squared and summed in double in a fixed order: no atomics, no
+ * dependence on launch order, two calls on the same data give the same bits.  With
+ * chunk = ceil((n / 4) / P) (integer n / 4), workgroup b owns the elements
+ * [4*b*chunk, min(4*(b+1)*chunk, 4*(n/4))), and the last one also the n % 4 elements at the
+ * end; an empty range stores 0.  P depends on n alone (64 <= P <= 256).
+ *
+ * of_adam_keras_dev_clip: of_adam_keras_dev with the gradient multiplier decided on the device.
+ * One wave sums the partials in index order (double), norm = grad_scale * sqrt(sum)
+ * (grad_scale: the 1/world of a data-parallel rank sum), and writes the state block
+ *   { double norm; float norm_f; float mult; int32 skip; int32 skipped_total; int32 pad[2]; }
+ * (of_adam_clip_state_bytes bytes, 8-byte aligned, zeroed once by the caller):
+ *   finite norm, clip_norm > 0:  mult = (float)(grad_scale * clip_norm / max(norm, clip_norm)),
+ *                                == grad_scale bitwise when norm <= clip_norm (also norm 0);
+ *   finite norm, clip_norm == 0: mult = grad_scale (the norm is only recorded);
+ *   non-finite norm (a NaN or inf anywhere in g), skip_nonfinite != 0: skip = 1,
+ *       skipped_total += 1, *iter and sched[1] are left alone and the arena update returns
+ *       before it touches p, m or v: the step did not happen;
+ *   non-finite norm, skip_nonfinite == 0: mult = NaN when clip_norm > 0 (every entry becomes
+ *       NaN, as tf.clip_by_global_norm documents), else grad_scale (the plain update).
+ * Unless skipped, t = ++*iter and sched[1] as of_adam_keras_dev, then the same arena update
+ * with g' = g * mult.  OF_EINVAL before any launch: a NULL pointer, n < 0, p / g / m / v not
+ * 16-byte aligned, npartials != of_grad_sumsq_partials(n), clip_norm negative or NaN. */
+int of_grad_sumsq_partials(int64_t n);
+int of_grad_sumsq(const float* g, int64_t n, double* partials, void* stream);
+size_t of_adam_clip_state_bytes(void);
+int of_adam_keras_dev_clip(float* p, const float* g, float* m, float* v, int64_t n, float* sched,
+                           int32_t* iter, float beta1, float beta2, float eps, float grad_scale,
+                           const double* partials, int npartials, float clip_norm,
+                           int skip_nonfinite, void* state, void* stream);
+
 /* Elementwise helpers used by the host glue. */
 int of_add_inplace(float* y, const float* x, int64_t n, void* stream);        /* y += x */
 int of_copy_strided(const float* src, int lds, float* dst, int ldd, int64_t npix, int c,

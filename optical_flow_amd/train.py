@@ -10,6 +10,8 @@ PNGs.  No TensorBoard writer (a JSONL step log instead).  Data parallelism (one 
 GPU, RCCL all-reduce of gradient buckets overlapped with the backward) is build-added; with
 KITTI each rank reads its own seeded shuffle.  ``--augment`` (KITTI only) switches on the
 seeded GPU augmentation of data_reader.AugmentOpts: random zoom / crop, flip, colour jitter.
+``--clip-norm C`` / ``--skip-nonfinite`` / ``--log-grad-norm`` switch on KerasAdam's global-norm
+clipping, its non-finite update guard and the per-step gradient norm in the step log.
 
 Run:  python -m optical_flow_amd.train --height 384 --width 512 --batch 8 --steps 20
       python -m optical_flow_amd.train --kitti /data/kitti_raw --epochs 20
@@ -30,7 +32,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import call
+from ._lib import call, lib
 from .data import synthetic_batch
 from .dist import GradBucketReducer, init_from_env
 from .loss import LossLayer
@@ -42,9 +44,28 @@ class KerasAdam:
     ResourceApplyAdam update with lr_t = lr*sqrt(1-b2^t)/(1-b1^t) (P13).  Two launches over
     the model's parameter arena: the step counter t and lr_t live in device memory
     (of_adam_keras_dev), so the same update also runs inside a captured HIP graph
-    (Trainer.graphed).  ``learning_rate`` may be set between steps (train.py:69-70)."""
+    (Trainer.graphed).  ``learning_rate`` may be set between steps (train.py:69-70).
 
-    def __init__(self, store, learning_rate=1e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
+    Build-added, all off by default (then ``apply_gradients`` is the one of_adam_keras_dev
+    call):
+
+    global_clipnorm: Keras's argument of that name, tf.clip_by_global_norm over all gradients:
+        with norm = the L2 norm of the whole (averaged) gradient, every gradient is multiplied
+        by global_clipnorm / max(norm, global_clipnorm).  A step whose norm is at or under the
+        threshold is bitwise the unclipped step.  As in TensorFlow, a non-finite norm (one inf
+        or NaN gradient element) makes the multiplier NaN and so every parameter NaN, unless
+        skip_nonfinite is set.  Settable between eager steps, like learning_rate.
+    skip_nonfinite: a step whose gradient norm is inf or NaN is dropped on the device:
+        parameters, both moments and the step counter stay bitwise as they were, and
+        ``skipped_updates`` counts it.
+    track_grad_norm: only record the norm (``last_grad_norm``).
+
+    With any of them on, the update is two calls, of_grad_sumsq and of_adam_keras_dev_clip: the
+    norm, the multiplier and the skip decision are formed on the device, with no host
+    read-back and no allocation after construction, so the update stays capturable."""
+
+    def __init__(self, store, learning_rate=1e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
+                 global_clipnorm=None, skip_nonfinite=False, track_grad_norm=False):
         self.store = store
         self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
         dev = store.arena.device
@@ -53,6 +74,60 @@ class KerasAdam:
         self._sched = torch.zeros(2, device=dev)              # [lr, lr_t of the last step]
         self._iter = torch.zeros(1, dtype=torch.int32, device=dev)
         self.learning_rate = learning_rate
+        self.global_clipnorm = global_clipnorm
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.track_grad_norm = bool(track_grad_norm)
+        self._partials = self._state = None
+        if self._clip_path():
+            self._alloc_clip()
+
+    @staticmethod
+    def check_global_clipnorm(value):
+        """None, or the positive finite float of ``global_clipnorm``; ValueError otherwise."""
+        if value is None:
+            return None
+        c = float(value)
+        if not (math.isfinite(c) and c > 0.0):
+            raise ValueError("global_clipnorm must be a positive finite number, got %r" % (value,))
+        return c
+
+    @property
+    def global_clipnorm(self):
+        return self._clipnorm
+
+    @global_clipnorm.setter
+    def global_clipnorm(self, value):
+        self._clipnorm = self.check_global_clipnorm(value)
+
+    def _clip_path(self):
+        return self._clipnorm is not None or self.skip_nonfinite or self.track_grad_norm
+
+    def _alloc_clip(self):
+        dev = self.store.arena.device
+        n = lib().of_grad_sumsq_partials(self.store.numel)
+        self._partials = torch.zeros(n, dtype=torch.float64, device=dev)
+        # the of_adam_keras_dev_clip state block (include/oflow.h): norm f64, norm f32, mult f32,
+        # skip i32, skipped_total i32
+        self._state = torch.zeros(lib().of_adam_clip_state_bytes() // 8, dtype=torch.float64,
+                                  device=dev)
+
+    def _clip_state(self):
+        if self._state is None:
+            raise RuntimeError("KerasAdam was built without global_clipnorm, skip_nonfinite or "
+                               "track_grad_norm: no gradient norm is computed")
+        return self._state
+
+    @property
+    def last_grad_norm(self):
+        """The global gradient norm of the last apply_gradients (of the averaged gradient under
+        data parallelism; inf or NaN for a non-finite gradient): a 0-dim float64 device tensor,
+        a view into the state block that every later step overwrites -- no sync until read."""
+        return self._clip_state()[0]
+
+    @property
+    def skipped_updates(self):
+        """Updates dropped by skip_nonfinite so far (device counter, read with a sync)."""
+        return int(self._clip_state().view(torch.int32)[5].item())
 
     @property
     def learning_rate(self):
@@ -70,11 +145,25 @@ class KerasAdam:
 
     def apply_gradients(self, grad_scale: float = 1.0):
         s = self.store
-        call("of_adam_keras_dev", C.c_void_p(s.arena.data_ptr()),
-             C.c_void_p(s.grad_arena.data_ptr()), C.c_void_p(self.m.data_ptr()),
-             C.c_void_p(self.v.data_ptr()), s.numel, C.c_void_p(self._sched.data_ptr()),
-             C.c_void_p(self._iter.data_ptr()), self.beta_1, self.beta_2, self.epsilon,
-             grad_scale, ops._stream())
+        if self._clip_path():
+            if self._state is None:      # switched on after construction (eager steps only)
+                self._alloc_clip()
+            stream = ops._stream()
+            call("of_grad_sumsq", C.c_void_p(s.grad_arena.data_ptr()), s.numel,
+                 C.c_void_p(self._partials.data_ptr()), stream)
+            call("of_adam_keras_dev_clip", C.c_void_p(s.arena.data_ptr()),
+                 C.c_void_p(s.grad_arena.data_ptr()), C.c_void_p(self.m.data_ptr()),
+                 C.c_void_p(self.v.data_ptr()), s.numel, C.c_void_p(self._sched.data_ptr()),
+                 C.c_void_p(self._iter.data_ptr()), self.beta_1, self.beta_2, self.epsilon,
+                 grad_scale, C.c_void_p(self._partials.data_ptr()), self._partials.numel(),
+                 self._clipnorm or 0.0, int(self.skip_nonfinite),
+                 C.c_void_p(self._state.data_ptr()), stream)
+        else:
+            call("of_adam_keras_dev", C.c_void_p(s.arena.data_ptr()),
+                 C.c_void_p(s.grad_arena.data_ptr()), C.c_void_p(self.m.data_ptr()),
+                 C.c_void_p(self.v.data_ptr()), s.numel, C.c_void_p(self._sched.data_ptr()),
+                 C.c_void_p(self._iter.data_ptr()), self.beta_1, self.beta_2, self.epsilon,
+                 grad_scale, ops._stream())
         s.version += 1       # packed conv weights are refreshed lazily on next use
         if getattr(s, "bn_guard", None) is not None:
             s.bn_guard.after_update(self._lr)
@@ -151,7 +240,13 @@ REPLAY_PRIO = None if _RP == "none" else int(_RP)
 class GraphedStep:
     """A captured Trainer.train_step.  ``batch`` is the static input: write the next batch
     into it (``load``) before calling.  Returns the static (loss, flows) tensors, overwritten
-    by every replay."""
+    by every replay.
+
+    Every host argument of the step is baked into the capture, the optimizer's
+    ``global_clipnorm``, ``skip_nonfinite`` and ``track_grad_norm`` among them: set them before
+    capturing (the learning rate is the exception, it lives in device memory).  The clip and
+    skip decisions themselves are taken on the device in every replay; ``last_grad_norm`` and
+    ``skipped_updates`` read the replays' results."""
 
     def __init__(self, trainer: "Trainer", batch_imgs, warmup: int = 2, capture_ctx=None):
         """capture_ctx: optional context-manager factory entered around the capture only (the
@@ -282,6 +377,12 @@ def build_parser():
                     help="census window radius r, a (2r+1) x (2r+1) window")
     ap.add_argument("--photometric-weight", type=float, default=1.0,
                     help="weight of the photometric L1 term (0 with --census-weight: census only)")
+    ap.add_argument("--clip-norm", type=float, default=None, metavar="C",
+                    help="clip the gradients to global L2 norm C (Keras global_clipnorm)")
+    ap.add_argument("--skip-nonfinite", action="store_true",
+                    help="drop an update whose gradient norm is inf or NaN")
+    ap.add_argument("--log-grad-norm", action="store_true",
+                    help="record the global gradient norm of every step in the step log")
     g = ap.add_argument_group(
         "augmentation (with --kitti only)", "seeded by --seed; both images of a pair get the "
         "same draw; an --aug-* flag without --augment starts from no augmentation")
@@ -324,18 +425,25 @@ def main(argv=None):
                                photometric_weight=args.photometric_weight)
     except ValueError as e:
         ap.error(str(e))
+    try:
+        KerasAdam.check_global_clipnorm(args.clip_norm)
+    except ValueError as e:
+        ap.error("--clip-norm: " + str(e))
+    clip = args.clip_norm is not None or args.skip_nonfinite or args.log_grad_norm
 
     rank, world, local = init_from_env()
     torch.cuda.set_device(local)
     net = build_flow_net(args.height, args.width, args.pretrained, seed=args.seed)
     if rank == 0:
         net.summary()
-    opt = KerasAdam(net.store, learning_rate=args.lr)
+    opt = KerasAdam(net.store, learning_rate=args.lr, global_clipnorm=args.clip_norm,
+                    skip_nonfinite=args.skip_nonfinite, track_grad_norm=args.log_grad_norm)
     trainer = Trainer(net, opt, loss_layer)
     log = open(args.log, "a") if (args.log and rank == 0) else None
     census = (args.census_weight != 0.0 or args.census_radius != 3 or
               args.photometric_weight != 1.0)
-    if log and (args.smoothness_weight or args.edge_alpha or augment is not None or census):
+    if log and (args.smoothness_weight or args.edge_alpha or augment is not None or census
+                or clip):
         # header record (no "step" key); a default run's log holds step records only, as before
         head = {"header": True, "smoothness_weight": args.smoothness_weight,
                 "edge_alpha": args.edge_alpha}
@@ -344,6 +452,9 @@ def main(argv=None):
                         photometric_weight=args.photometric_weight)
         if augment is not None:
             head["augment"] = augment.as_dict()
+        if clip:
+            head.update(clip_norm=args.clip_norm, skip_nonfinite=args.skip_nonfinite,
+                        log_grad_norm=args.log_grad_norm)
         log.write(json.dumps(head) + "\n")
     reader = None
     if args.kitti:
@@ -368,7 +479,13 @@ def main(argv=None):
                 sys.stdout.write("\rbatch %d/%d, loss: %.2e    " % (b + 1, nbatches, lv))
                 sys.stdout.flush()
                 if log:
-                    log.write(json.dumps({"step": step, "loss": lv, "t": time.time() - t0}) + "\n")
+                    rec = {"step": step, "loss": lv, "t": time.time() - t0}
+                    if clip:
+                        # read where the loss was just read (the step is complete): the state
+                        # block of this step, no further sync point
+                        rec["grad_norm"] = float(opt.last_grad_norm)
+                        rec["skipped"] = opt.skipped_updates
+                    log.write(json.dumps(rec) + "\n")
                 if args.display_dir and (b + 1) % 10 == 0:
                     from .drawing import display_training
                     display_training(batch, flows, args.display_dir, step)

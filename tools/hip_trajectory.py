@@ -3,6 +3,8 @@
 python tools/hip_trajectory.py --steps 26 [--det] [--precision fp32] --out gpurun_out/traj.jsonl
     [--smoothness-weight 0.2 --edge-alpha 10]      (the loss with the smoothness term on)
     [--census-weight 1 --census-radius 3 --photometric-weight 1]    (with the census term on)
+    [--clip-norm C] [--skip-nonfinite] [--track-grad-norm]   (KerasAdam's global_clipnorm, the
+        non-finite guard, the norm alone; each adds grad_norm and skipped to every record)
 
 Same weights, batch and optimizer as bench.py and tools/oracle_trajectory.py; one JSON line
 per step: loss and mean / max |flow| per level of that step's forward (the weights before the
@@ -37,6 +39,9 @@ def main():
     ap.add_argument("--census-weight", type=float, default=0.0)
     ap.add_argument("--census-radius", type=int, default=3)
     ap.add_argument("--photometric-weight", type=float, default=1.0)
+    ap.add_argument("--clip-norm", type=float, default=None)
+    ap.add_argument("--skip-nonfinite", action="store_true")
+    ap.add_argument("--track-grad-norm", action="store_true")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     from optical_flow_amd import _lib, ops
@@ -50,7 +55,10 @@ def main():
     H, W, B = args.height, args.width, args.batch
     vals = init_params(flow_net_spec(levels=4), 0)
     net = FlowNet(H, W, values=vals, precision=args.precision)
-    trainer = Trainer(net, KerasAdam(net.store),
+    clip = args.clip_norm is not None or args.skip_nonfinite or args.track_grad_norm
+    trainer = Trainer(net, KerasAdam(net.store, global_clipnorm=args.clip_norm,
+                                     skip_nonfinite=args.skip_nonfinite,
+                                     track_grad_norm=args.track_grad_norm),
                       LossLayer(args.smoothness_weight, args.edge_alpha,
                                 census_weight=args.census_weight,
                                 census_radius=args.census_radius,
@@ -87,6 +95,10 @@ def main():
                         "flow_abs_mean": [round(float(fl.abs().mean()), 6) for fl in flows],
                         "flow_abs_max": [round(float(fl.abs().max()), 4) for fl in flows],
                         "sec": round(time.time() - t0, 3)})
+            if clip:
+                rec.update({"clip_norm": args.clip_norm,
+                            "grad_norm": float(trainer.optimizer.last_grad_norm),
+                            "skipped": trainer.optimizer.skipped_updates})
             f.write(json.dumps(rec) + "\n")
             f.flush()
             print(json.dumps(rec), flush=True)
