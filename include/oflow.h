@@ -306,6 +306,44 @@ int of_warp_bwd_det(const float* dout, const float* inp, int n, int h, int w, in
                     const float* dflow_add, int ld_add, void* workspace, size_t ws_bytes,
                     void* stream);
 
+/* The warp convention: which grid the flow is added to.  OF_WARP_REFERENCE is the reference's
+ * transposed grid (P1), what every entry point without a convention argument samples with:
+ *   x = i + flow[b,i,j,0] (i = ROW index), y = j + flow[b,i,j,1] (j = COLUMN index).
+ * OF_WARP_IMAGE is image coordinates -- flow[...,0] is the x (column) displacement from image 1
+ * to image 2 and flow[...,1] the y (row) displacement, so a zero flow is the identity:
+ *   x = j + flow[b,i,j,0] (column),  y = i + flow[b,i,j,1] (row),
+ *   out[b,i,j] = bilinear(inp[b], x, y).
+ * Everything after the sum is the same arithmetic in both (P2): the coordinate formed in
+ * float32, floor, x0 / x1 / y0 / y1 clipped, weights from the clipped x1 / y1 and the unclipped
+ * x / y, no gradient through floor; d(flow) keeps its channel meaning (d/dx, d/dy).  The _cv
+ * entry points below take `int convention`; any other value returns OF_EINVAL before anything
+ * is launched or written, and convention 0 is bitwise the entry point without the suffix. */
+#define OF_WARP_REFERENCE 0
+#define OF_WARP_IMAGE 1
+/* of_warp_fwd in the given convention (OF_WARP_IMAGE: out[b,i,j] = bilinear(inp[b],
+ * x = j + flow[b,i,j,0], y = i + flow[b,i,j,1])). */
+int of_warp_fwd_cv(const float* inp, int n, int h, int w, int c, const float* flow, float* out,
+                   int convention, void* stream);
+/* of_warp_bwd (dflow_add NULL) and of_warp_bwd_add (dflow_add given, row stride ld_add) of that
+ * sampler (OF_WARP_IMAGE: x = j + flow[b,i,j,0], y = i + flow[b,i,j,1]): dinp += scatter
+ * (atomics), dflow = d/d(flow) (+ dflow_add), written. */
+int of_warp_bwd_cv(const float* dout, const float* inp, int n, int h, int w, int c,
+                   const float* flow, float* dinp, float* dflow, const float* dflow_add,
+                   int ld_add, int convention, void* stream);
+/* of_warp_bwd_det for relative flows in the given convention (OF_WARP_IMAGE: x = j +
+ * flow[b,i,j,0], y = i + flow[b,i,j,1]); same workspace and header.  In the image convention
+ * the window is mode A only: a (source, corner) entry lies within R of its source in both axes,
+ * so destination (r, x) sums the sources of rows r +- R, columns x +- R (clipped), on borders
+ * and corners too -- no far-edge extension, no piles, nothing left out of the 4 x 4 tiles but
+ * the bins that overflow.  For R above key 28, key 28 = 0 or h, w >= 65536 the fixed-point
+ * path serves (no mode B is built for this convention); the header reads as before and
+ * needs no new slot: R <= key 28 means mode A served; else the hit count stays 0 (never
+ * 4 n h w) and the fixed-point path did. */
+int of_warp_bwd_det_cv(const float* dout, const float* inp, int n, int h, int w, int c,
+                       const float* flow, float* dinp, float* dflow, const float* dflow_add,
+                       int ld_add, int convention, void* workspace, size_t ws_bytes,
+                       void* stream);
+
 /* upscale_flow (model.py:76-77; P6, P7): out = resize_bilinear_x2(in) * scale, half-pixel
  * centres.  in: [n][h][w][c] dense, out: [n][2h][2w] pixels of ldo (channel slice). */
 int of_upscale2x_fwd(const float* in, int n, int h, int w, int c, float scale, float* out,
@@ -349,6 +387,15 @@ int of_photo_l1_bwd_multi(const float* const* img6s, const float* const* flows, 
                           const int* hs, const int* ws, int levels, const float* coefs,
                           const float* dloss, float* const* dflows, const int* lds,
                           void* stream);
+/* The two above with the warp in the given convention (OF_WARP_IMAGE: the photometric sample
+ * of pixel (i, j) is x = j + flow[b,i,j,0], y = i + flow[b,i,j,1]). */
+int of_photo_l1_fwd_multi_cv(const float* const* img6s, const float* const* flows, int n,
+                             const int* hs, const int* ws, int levels, float* partials,
+                             int convention, void* stream);
+int of_photo_l1_bwd_multi_cv(const float* const* img6s, const float* const* flows, int n,
+                             const int* hs, const int* ws, int levels, const float* coefs,
+                             const float* dloss, float* const* dflows, const int* lds,
+                             int convention, void* stream);
 int of_sum_partials(const float* const* parts, const int* counts, const float* coefs,
                     int ngroups, float* out, void* stream);
 
@@ -404,6 +451,12 @@ int of_census_fwd_multi(const float* const* img6s, const float* const* flows, in
                         const int* hs, const int* ws, int levels, int radius,
                         const float* coefs, float* const* workspaces, float* const* dcdfs,
                         float* partials, void* stream);
+/* of_census_fwd_multi with u sampled in the given warp convention (OF_WARP_IMAGE: x = j +
+ * flow[b,i,j,0], y = i + flow[b,i,j,1]); the backward does not sample and has no such form. */
+int of_census_fwd_multi_cv(const float* const* img6s, const float* const* flows, int n,
+                           const int* hs, const int* ws, int levels, int radius,
+                           const float* coefs, float* const* workspaces, float* const* dcdfs,
+                           float* partials, int convention, void* stream);
 int of_census_bwd_multi(const float* const* dcdfs, int n, const int* hs, const int* ws,
                         int levels, const float* coefs, const float* dloss,
                         float* const* dflows, const int* lds, int accumulate, void* stream);
@@ -523,7 +576,9 @@ int of_timing_enable(int on);
  * 0 = never);
  * key 28 = of_warp_bwd_det's window gather: mode A (a window of radius R around the
  * transposed position) when R = floor(max |flow|) + 2 <= this, else mode B (default 8; 0 =
- * no window, always the fixed-point path; 1 = always mode B);
+ * no window, always the fixed-point path; 1 = always mode B); in the image convention
+ * (OF_WARP_IMAGE) mode A is a window of radius R around the destination's own position when
+ * R <= this, and above it the fixed-point path runs (there is no mode B);
  * key 29 = wgrad_reduce lane rule (0 = default, 1-4 = the measured alternatives);
  * key 30 = the split implicit GEMMs (conv_gemm_x3: stride-2 and 1x1 layers) on an LDS-DMA ring
  * with both operands DMA'd: 3 slots, one chunk in flight across each barrier (1), or 2 slots,
@@ -539,7 +594,9 @@ int of_timing_enable(int on);
  * key 34 = of_warp_bwd_det mode A by 4 x 4 destination tiles with LDS-binned sources in a
  * kernel of their own, own_tile, the last row / column and overflowed bins then scanned by
  * own_window (2, default), the tiles inside own_window (1), or the per-destination window scan
- * (0); bitwise the same results;
+ * (0); bitwise the same results; in the image convention the same three forms, every
+ * destination binned by the tiles (no row or column is left to the scan), the rest pass
+ * scanning the overflowed bins alone;
  * key 35 = that tiled form with its d(flow) loads issued first (1) or after the gather (0,
  * default); bitwise the same results;
  * key 36 = the fp32 split 3x3 form for 64-column N tiles: 0 (default) conv_tile_x3<64, 4, 2,

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("OFLOW_LIB") or os.path.join(HERE, "liboflow.so")
 OF_OK, OF_EINVAL, OF_EHIP, OF_EUNSUPPORTED, OF_ETIMEOUT = 0, 1, 2, 3, 4
 OF_REDUCE_SUM, OF_REDUCE_AVG = 0, 1         # of_comm_allreduce_ex_async op
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
+WARP_REFERENCE, WARP_IMAGE = 0, 1           # OF_WARP_REFERENCE / OF_WARP_IMAGE of the _cv entries
 
 
 class B16iIO(C.Structure):
@@ -112,6 +113,10 @@ PROTOTYPES = {
     "of_warp_bwd_det_workspace": (SZ, [I, I, I, I]),
     "of_warp_bwd_det_header": (SZ, [I, I, I, I]),
     "of_warp_bwd_det": (I, [P, P, I, I, I, I, P, I, P, P, P, I, P, SZ, P]),
+    # the same with an explicit warp convention (WARP_REFERENCE / WARP_IMAGE)
+    "of_warp_fwd_cv": (I, [P, I, I, I, I, P, P, I, P]),
+    "of_warp_bwd_cv": (I, [P, P, I, I, I, I, P, P, P, P, I, I, P]),
+    "of_warp_bwd_det_cv": (I, [P, P, I, I, I, I, P, P, P, P, I, I, P, SZ, P]),
     "of_upscale2x_fwd": (I, [P, I, I, I, I, F, P, I, P]),
     "of_upscale2x_bwd": (I, [P, I, I, I, I, I, F, P, I, P]),
     "of_upscale2x_bwd_ld": (I, [P, I, I, I, I, I, F, P, I, I, P]),
@@ -172,6 +177,10 @@ PROTOTYPES = {
                                   P]),
     "of_photo_l1_bwd_multi": (I, [C.POINTER(P), C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I,
                                   C.POINTER(F), P, C.POINTER(P), C.POINTER(I), P]),
+    "of_photo_l1_fwd_multi_cv": (I, [C.POINTER(P), C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I,
+                                     P, I, P]),
+    "of_photo_l1_bwd_multi_cv": (I, [C.POINTER(P), C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I,
+                                     C.POINTER(F), P, C.POINTER(P), C.POINTER(I), I, P]),
     "of_flow_smooth_partials": (I, [I, I, I]),
     "of_flow_smooth_fwd_multi": (I, [C.POINTER(P), C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I,
                                      F, F, C.POINTER(F), C.POINTER(F), P, P]),
@@ -182,6 +191,8 @@ PROTOTYPES = {
     "of_census_workspace_floats": (I, [I, I, I]),
     "of_census_fwd_multi": (I, [C.POINTER(P), C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I, I,
                                 C.POINTER(F), C.POINTER(P), C.POINTER(P), P, P]),
+    "of_census_fwd_multi_cv": (I, [C.POINTER(P), C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I, I,
+                                   C.POINTER(F), C.POINTER(P), C.POINTER(P), P, I, P]),
     "of_census_bwd_multi": (I, [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I, C.POINTER(F), P,
                                 C.POINTER(P), C.POINTER(I), I, P]),
     "of_stem_bwd_fused_workspace": (SZ, [PD, I]),

@@ -42,14 +42,16 @@ __device__ __forceinline__ float census_mean3(float a, float b, float c) {
   return (a + b + c) * (CN_S / 3.f);
 }
 
-// g1, u and du/d(flow) of pixel (i, j) of the image starting at pixel offset img
+// g1, u and du/d(flow) of pixel (i, j) of the image starting at pixel offset img (CV: the
+// warp convention, warp_tap.h)
+template <int CV>
 __device__ __forceinline__ void census_sample(const float* __restrict__ img6,
                                               const float* __restrict__ flow, int i, int j,
                                               int h, int w, int64_t img, float2& gu,
                                               float2& du) {
   const int64_t p = img + (int64_t)i * w + j;
   const float2 f = *reinterpret_cast<const float2*>(flow + 2 * p);
-  const WarpTap t = warp_tap(i, j, f.x, f.y, h, w, img);
+  const WarpTap t = warp_tap<CV>(i, j, f.x, f.y, h, w, img);
   const float a = t.a, b = t.b;
   const float w00 = a * b, w01 = a * (1.f - b), w10 = (1.f - a) * b,
               w11 = (1.f - a) * (1.f - b);
@@ -76,7 +78,7 @@ __device__ __forceinline__ float census_tau(float d, float r) {
   return d * r;
 }
 
-template <int R>
+template <int R, int CV>
 __global__ __launch_bounds__(CN_THREADS) void census_fwd_multi(CensusMulti m,
                                                                float* __restrict__ partials) {
   constexpr int HW = CN_TX + 2 * R, HH = CN_TY + 2 * R;
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(CN_THREADS) void census_fwd_multi(CensusMulti m,
   for (int k = threadIdx.x; k < HH * HW; k += CN_THREADS) {
     const int y = y0 - R + k / HW, x = x0 - R + k % HW;
     float2 gu = make_float2(0.f, 0.f), du = make_float2(0.f, 0.f);
-    if (y >= 0 && y < h && x >= 0 && x < w) census_sample(img6, flow, y, x, h, w, img, gu, du);
+    if (y >= 0 && y < h && x >= 0 && x < w) census_sample<CV>(img6, flow, y, x, h, w, img, gu, du);
     s_gu[k] = gu;
     s_du[k] = du;
   }
@@ -206,7 +208,17 @@ int of_census_fwd_multi(const float* const* img6s, const float* const* flows, in
                         const int* hs, const int* ws, int levels, int radius,
                         const float* coefs, float* const* workspaces, float* const* dcdfs,
                         float* partials, void* stream) {
+  return of_census_fwd_multi_cv(img6s, flows, n, hs, ws, levels, radius, coefs, workspaces, dcdfs,
+                                partials, OF_WARP_REFERENCE, stream);
+}
+
+int of_census_fwd_multi_cv(const float* const* img6s, const float* const* flows, int n,
+                           const int* hs, const int* ws, int levels, int radius,
+                           const float* coefs, float* const* workspaces, float* const* dcdfs,
+                           float* partials, int convention, void* stream) {
   static const std::string fn = "of_census_fwd_multi";
+  if (convention != OF_WARP_REFERENCE && convention != OF_WARP_IMAGE)
+    return fail(OF_EINVAL, fn + ": unknown warp convention");
   CensusMulti m{};
   const int st = census_args(fn, n, hs, ws, levels, coefs, m);
   if (st) return st;
@@ -231,12 +243,11 @@ int of_census_fwd_multi(const float* const* img6s, const float* const* flows, in
   }
   if (m.beg[levels] >= INT32_MAX) return fail(OF_EINVAL, fn + ": too many blocks");
   const dim3 grid((unsigned)m.beg[levels]), block(CN_THREADS);
-  if (radius == 1)
-    hipLaunchKernelGGL(census_fwd_multi<1>, grid, block, 0, as_stream(stream), m, partials);
-  else if (radius == 2)
-    hipLaunchKernelGGL(census_fwd_multi<2>, grid, block, 0, as_stream(stream), m, partials);
-  else
-    hipLaunchKernelGGL(census_fwd_multi<3>, grid, block, 0, as_stream(stream), m, partials);
+  const bool im = convention == OF_WARP_IMAGE;
+  auto k = radius == 1   ? (im ? census_fwd_multi<1, WARP_CV_IMAGE> : census_fwd_multi<1, WARP_CV_REFERENCE>)
+           : radius == 2 ? (im ? census_fwd_multi<2, WARP_CV_IMAGE> : census_fwd_multi<2, WARP_CV_REFERENCE>)
+                         : (im ? census_fwd_multi<3, WARP_CV_IMAGE> : census_fwd_multi<3, WARP_CV_REFERENCE>);
+  hipLaunchKernelGGL(k, grid, block, 0, as_stream(stream), m, partials);
   return check_launch("census_fwd_multi");
 }
 

@@ -963,7 +963,7 @@ __global__ __launch_bounds__(FB_NT, 1) void corr_bwd_fused(CorrFusedArgs a) {
 // One thread per (pixel, channel quad); C % 4 == 0.
 // I: index type, 32-bit unsigned when the element count fits (64-bit divisions per element
 // made the kernel ALU-bound)
-template <typename I>
+template <typename I, int CV>
 __global__ __launch_bounds__(256) void warp_fwd_vec(const float* __restrict__ inp, int n, int h,
                                                     int w, int c,
                                                     const float* __restrict__ flow,
@@ -979,7 +979,7 @@ __global__ __launch_bounds__(256) void warp_fwd_vec(const float* __restrict__ in
     const int i = (int)(t2 % (I)h);
     const int64_t img = (int64_t)(t2 / (I)h) * h * w;
     const float2 f = *reinterpret_cast<const float2*>(flow + 2 * p);
-    const WarpTap t = warp_tap(i, j, f.x, f.y, h, w, img, absolute);
+    const WarpTap t = warp_tap<CV>(i, j, f.x, f.y, h, w, img, absolute);
     const float4 v00 = *reinterpret_cast<const float4*>(inp + t.o00 * c + 4 * q);
     const float4 v01 = *reinterpret_cast<const float4*>(inp + t.o01 * c + 4 * q);
     const float4 v10 = *reinterpret_cast<const float4*>(inp + t.o10 * c + 4 * q);
@@ -996,6 +996,7 @@ __global__ __launch_bounds__(256) void warp_fwd_vec(const float* __restrict__ in
 }
 
 // Generic channel count: one thread per pixel.
+template <int CV>
 __global__ __launch_bounds__(256) void warp_fwd_scalar(const float* __restrict__ inp, int n,
                                                        int h, int w, int c,
                                                        const float* __restrict__ flow,
@@ -1007,7 +1008,7 @@ __global__ __launch_bounds__(256) void warp_fwd_scalar(const float* __restrict__
     const int64_t t2 = p / w;
     const int i = (int)(t2 % h);
     const int64_t img = (t2 / h) * h * w;
-    const WarpTap t = warp_tap(i, j, flow[2 * p], flow[2 * p + 1], h, w, img, absolute);
+    const WarpTap t = warp_tap<CV>(i, j, flow[2 * p], flow[2 * p + 1], h, w, img, absolute);
     const float w00 = t.a * t.b, w01 = t.a * (1.f - t.b);
     const float w10 = (1.f - t.a) * t.b, w11 = (1.f - t.a) * (1.f - t.b);
     for (int e = 0; e < c; ++e)
@@ -1020,6 +1021,7 @@ __global__ __launch_bounds__(256) void warp_fwd_scalar(const float* __restrict__
 // 64 consecutive floats each (256 contiguous bytes per atomic wave-instruction: the shape
 // that runs at the chip-wide atomic rate), loads are coalesced rows, and d(flow) is a
 // 64-lane xor-shuffle reduction.  dinp scatter with fp32 atomics (GatherNd's adjoint).
+template <int CV>
 __global__ __launch_bounds__(256) void warp_bwd_wave(const float* __restrict__ dout,
                                                      const float* __restrict__ inp, int n,
                                                      int h, int w, int c,
@@ -1037,7 +1039,7 @@ __global__ __launch_bounds__(256) void warp_bwd_wave(const float* __restrict__ d
     const int i = (int)(t2 % h);
     const int64_t img = (t2 / h) * h * w;
     const float2 f = *reinterpret_cast<const float2*>(flow + 2 * p);
-    const WarpTap t = warp_tap(i, j, f.x, f.y, h, w, img, absolute);
+    const WarpTap t = warp_tap<CV>(i, j, f.x, f.y, h, w, img, absolute);
     const float a = t.a, b = t.b;
     const float w00 = a * b, w01 = a * (1.f - b), w10 = (1.f - a) * b,
                 w11 = (1.f - a) * (1.f - b);
@@ -1084,6 +1086,7 @@ __global__ __launch_bounds__(256) void warp_bwd_wave(const float* __restrict__ d
 // the workgroup as one add per destination instead of one per pixel and corner.
 constexpr int WH_T = 8, WH_SLOTS = 64, WH_WAVES = 16;
 
+template <int CV>
 __global__ __launch_bounds__(64 * WH_WAVES) void warp_bwd_agg(const float* __restrict__ dout,
                                                     const float* __restrict__ inp, int n, int h,
                                                     int w, int c,
@@ -1117,7 +1120,8 @@ __global__ __launch_bounds__(64 * WH_WAVES) void warp_bwd_agg(const float* __res
       if (i >= h || j >= w) continue;                 // wave-uniform
       const int64_t p = img + (int64_t)i * w + j;
       const float2 f = *reinterpret_cast<const float2*>(flow + 2 * p);
-      const float x = (float)i + f.x, y = (float)j + f.y;
+      const float x = (float)(CV == WARP_CV_IMAGE ? j : i) + f.x;
+      const float y = (float)(CV == WARP_CV_IMAGE ? i : j) + f.y;
       const int xi = (int)fmaxf(fminf(floorf(x), 2147483520.f), -2147483520.f);
       const int yi = (int)fmaxf(fminf(floorf(y), 2147483520.f), -2147483520.f);
       const int x0 = min(max(xi, 0), w - 1), x1 = min(max(xi + 1, 0), w - 1);
@@ -1236,6 +1240,7 @@ __device__ __forceinline__ float row16_sum(float v) {   // sum over the 16 lanes
   return v;                                              // row_ror 8, 4, 2, 1
 }
 
+template <int CV>
 __global__ __launch_bounds__(WG_NT) WARP_WPE void warp_bwd_gather(const float* __restrict__ dout,
                                                          const float* __restrict__ inp, int n,
                                                          int h, int w, int c,
@@ -1261,10 +1266,12 @@ __global__ __launch_bounds__(WG_NT) WARP_WPE void warp_bwd_gather(const float* _
   const int i0 = (rem / tiles_j) * WG_T, j0 = (rem % tiles_j) * WG_T;
   const int64_t img = (int64_t)b * h * w;
 
-  // corners of pixel (i, j): rows {y0, y1} x columns {x0, x1} (the reference's transposed grid)
+  // corners of pixel (i, j): rows {y0, y1} x columns {x0, x1} (CV 0: the reference's transposed
+  // grid; CV 1: the image convention, warp_tap.h)
   auto corners = [&](int i, int j, float2 f, int& y0, int& y1, int& x0, int& x1, float& a,
                      float& bq) {
-    const float x = (float)i + f.x, y = (float)j + f.y;
+    const float x = (float)(CV == WARP_CV_IMAGE ? j : i) + f.x;
+    const float y = (float)(CV == WARP_CV_IMAGE ? i : j) + f.y;
     const int xi = (int)fmaxf(fminf(floorf(x), 2147483520.f), -2147483520.f);
     const int yi = (int)fmaxf(fminf(floorf(y), 2147483520.f), -2147483520.f);
     x0 = min(max(xi, 0), w - 1), x1 = min(max(xi + 1, 0), w - 1);
@@ -1453,6 +1460,7 @@ __global__ __launch_bounds__(WG_NT) WARP_WPE void warp_bwd_gather(const float* _
   }
 }
 
+template <int CV>
 __global__ __launch_bounds__(256) void warp_bwd_scalar(const float* __restrict__ dout,
                                                        const float* __restrict__ inp, int n,
                                                        int h, int w, int c,
@@ -1467,7 +1475,7 @@ __global__ __launch_bounds__(256) void warp_bwd_scalar(const float* __restrict__
     const int64_t t2 = p / w;
     const int i = (int)(t2 % h);
     const int64_t img = (t2 / h) * h * w;
-    const WarpTap t = warp_tap(i, j, flow[2 * p], flow[2 * p + 1], h, w, img, absolute);
+    const WarpTap t = warp_tap<CV>(i, j, flow[2 * p], flow[2 * p + 1], h, w, img, absolute);
     const float a = t.a, b = t.b;
     float gx = 0.f, gy = 0.f;
     for (int e = 0; e < c; ++e) {
@@ -1657,10 +1665,11 @@ __global__ __launch_bounds__(256) void split_pair_kernel(const float* __restrict
 constexpr int PL_THREADS = 256;
 constexpr int PL_PIX_PER_BLOCK = 1024;
 
+template <int CV = WARP_CV_REFERENCE>
 __device__ __forceinline__ void photo_sample(const float* img6, int64_t p, int i, int j,
                                              float f0, float f1, int h, int w, int64_t img,
                                              float* diff, WarpTap& t, float v[4][3]) {
-  t = warp_tap(i, j, f0, f1, h, w, img);
+  t = warp_tap<CV>(i, j, f0, f1, h, w, img);
   const float a = t.a, b = t.b;
   const float w00 = a * b, w01 = a * (1.f - b), w10 = (1.f - a) * b,
               w11 = (1.f - a) * (1.f - b);
@@ -1719,6 +1728,7 @@ struct PhotoMulti {
   int64_t beg[9];
   int levels;
 };
+template <int CV>
 __global__ __launch_bounds__(PL_THREADS) void photo_l1_fwd_multi(int n, PhotoMulti m,
                                                                  float* __restrict__ partials) {
   int l = 0;
@@ -1738,7 +1748,7 @@ __global__ __launch_bounds__(PL_THREADS) void photo_l1_fwd_multi(int n, PhotoMul
     const int64_t img = (t2 / h) * h * w;
     float diff[3], v[4][3];
     WarpTap t;
-    photo_sample(img6, p, i, j, flow[2 * p], flow[2 * p + 1], h, w, img, diff, t, v);
+    photo_sample<CV>(img6, p, i, j, flow[2 * p], flow[2 * p + 1], h, w, img, diff, t, v);
     s += fabsf(diff[0]) + fabsf(diff[1]) + fabsf(diff[2]);
   }
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
@@ -1752,6 +1762,7 @@ __global__ __launch_bounds__(PL_THREADS) void photo_l1_fwd_multi(int n, PhotoMul
   }
 }
 
+template <int CV>
 __global__ __launch_bounds__(256) void photo_l1_bwd_multi(int n, PhotoMulti m,
                                                           const float* __restrict__ dloss) {
   const int64_t total = m.beg[m.levels];
@@ -1770,7 +1781,7 @@ __global__ __launch_bounds__(256) void photo_l1_bwd_multi(int n, PhotoMulti m,
     const int64_t img = (t2 / h) * h * w;
     float diff[3], v[4][3];
     WarpTap t;
-    photo_sample(img6, p, i, j, flow[2 * p], flow[2 * p + 1], h, w, img, diff, t, v);
+    photo_sample<CV>(img6, p, i, j, flow[2 * p], flow[2 * p + 1], h, w, img, diff, t, v);
     const float a = t.a, b = t.b, coef = m.coef[l] * dl;
     float gx = 0.f, gy = 0.f;
 #pragma unroll
@@ -2116,6 +2127,9 @@ int of_corr_concat_bwd(const float* dcat, int cp, const float* f1, const float* 
   return OF_OK;
 }
 
+// CV: the grid the flow is added to (warp_tap.h); the callers checked it.
+extern "C++" {
+template <int CV>
 static int warp_fwd_impl(const float* inp, int n, int h, int w, int c, const float* flow,
                          float* out, int absolute, void* stream) {
   OF_CHECK_ARG(inp && flow && out, "warp fwd: NULL pointer");
@@ -2125,30 +2139,42 @@ static int warp_fwd_impl(const float* inp, int n, int h, int w, int c, const flo
   if (c % 4 == 0 && ((uintptr_t)inp & 15) == 0 && ((uintptr_t)out & 15) == 0) {
     const int64_t total = npix * (c / 4);
     if (total + (int64_t)grid_for(total) * 256 < (int64_t)UINT32_MAX)
-      hipLaunchKernelGGL(warp_fwd_vec<uint32_t>, dim3(grid_for(total)), dim3(256), 0, s, inp, n,
+      hipLaunchKernelGGL((warp_fwd_vec<uint32_t, CV>), dim3(grid_for(total)), dim3(256), 0, s, inp, n,
                          h, w, c, flow, out, absolute);
     else
-      hipLaunchKernelGGL(warp_fwd_vec<int64_t>, dim3(grid_for(total)), dim3(256), 0, s, inp, n,
+      hipLaunchKernelGGL((warp_fwd_vec<int64_t, CV>), dim3(grid_for(total)), dim3(256), 0, s, inp, n,
                          h, w, c, flow, out, absolute);
   } else {
-    hipLaunchKernelGGL(warp_fwd_scalar, dim3(grid_for(npix)), dim3(256), 0, s, inp, n, h, w, c,
+    hipLaunchKernelGGL(warp_fwd_scalar<CV>, dim3(grid_for(npix)), dim3(256), 0, s, inp, n, h, w, c,
                        flow, out, absolute);
   }
   return check_launch("warp_fwd");
 }
+}  // extern "C++"
 
 int of_warp_fwd(const float* inp, int n, int h, int w, int c, const float* flow, float* out,
                 void* stream) {
-  return warp_fwd_impl(inp, n, h, w, c, flow, out, 0, stream);
+  return of_warp_fwd_cv(inp, n, h, w, c, flow, out, OF_WARP_REFERENCE, stream);
+}
+
+int of_warp_fwd_cv(const float* inp, int n, int h, int w, int c, const float* flow, float* out,
+                   int convention, void* stream) {
+  OF_CHECK_ARG(convention == OF_WARP_REFERENCE || convention == OF_WARP_IMAGE,
+               "warp fwd: unknown warp convention");
+  return convention == OF_WARP_IMAGE
+             ? warp_fwd_impl<WARP_CV_IMAGE>(inp, n, h, w, c, flow, out, 0, stream)
+             : warp_fwd_impl<WARP_CV_REFERENCE>(inp, n, h, w, c, flow, out, 0, stream);
 }
 
 int of_bilinear_fwd(const float* inp, int n, int h, int w, int c, const float* pts, float* out,
                     void* stream) {
-  return warp_fwd_impl(inp, n, h, w, c, pts, out, 1, stream);
+  return warp_fwd_impl<WARP_CV_REFERENCE>(inp, n, h, w, c, pts, out, 1, stream);
 }
 
 // dfa (row stride ldfa, 2 channels), when given, is added to d(flow): the gradient of the flow
 // through its other consumer (the concat's flow slice), so no separate add pass runs.
+extern "C++" {
+template <int CV>
 static int warp_bwd_impl(const float* dout, const float* inp, int n, int h, int w, int c,
                          const float* flow, float* dinp, float* dflow, int absolute,
                          void* stream, const float* dfa = nullptr, int ldfa = 0) {
@@ -2169,41 +2195,56 @@ static int warp_bwd_impl(const float* dout, const float* inp, int n, int h, int 
       const int64_t blocks =
           (int64_t)n * ((h + WG_T - 1) / WG_T) * ((w + WG_T - 1) / WG_T) * (c / 64);
       OF_CHECK_ARG(blocks < INT32_MAX, "warp bwd: too many tiles");
-      hipLaunchKernelGGL(warp_bwd_gather, dim3((unsigned)blocks), dim3(WG_NT), 0, s, dout,
+      hipLaunchKernelGGL(warp_bwd_gather<CV>, dim3((unsigned)blocks), dim3(WG_NT), 0, s, dout,
                          inp, n, h, w, c, flow, dinp, dflow, c == 64 ? dfa : nullptr, ldfa);
     } else {
       const int64_t blocks =
           (int64_t)n * ((h + WH_T - 1) / WH_T) * ((w + WH_T - 1) / WH_T) * (c / 64);
       OF_CHECK_ARG(blocks < INT32_MAX, "warp bwd: too many tiles");
-      hipLaunchKernelGGL(warp_bwd_agg, dim3((unsigned)blocks), dim3(64 * WH_WAVES), 0, s, dout,
+      hipLaunchKernelGGL(warp_bwd_agg<CV>, dim3((unsigned)blocks), dim3(64 * WH_WAVES), 0, s, dout,
                          inp, n, h, w, c, flow, dinp, dflow, c == 64 ? dfa : nullptr, ldfa);
     }
   } else if (c >= 16) {
     const int g = grid_for(npix * 64, 256, 16384);
-    hipLaunchKernelGGL(warp_bwd_wave, dim3(g), dim3(256), 0, s, dout, inp, n, h, w, c, flow,
+    hipLaunchKernelGGL(warp_bwd_wave<CV>, dim3(g), dim3(256), 0, s, dout, inp, n, h, w, c, flow,
                        dinp, dflow, absolute, dfa, ldfa);
   } else {
-    hipLaunchKernelGGL(warp_bwd_scalar, dim3(grid_for(npix)), dim3(256), 0, s, dout, inp, n, h,
+    hipLaunchKernelGGL(warp_bwd_scalar<CV>, dim3(grid_for(npix)), dim3(256), 0, s, dout, inp, n, h,
                        w, c, flow, dinp, dflow, absolute, dfa, ldfa);
   }
   return check_launch("warp_bwd");
 }
+}  // extern "C++"
 
 int of_warp_bwd(const float* dout, const float* inp, int n, int h, int w, int c,
                 const float* flow, float* dinp, float* dflow, void* stream) {
-  return warp_bwd_impl(dout, inp, n, h, w, c, flow, dinp, dflow, 0, stream);
+  return of_warp_bwd_cv(dout, inp, n, h, w, c, flow, dinp, dflow, nullptr, 0, OF_WARP_REFERENCE,
+                        stream);
+}
+
+int of_warp_bwd_cv(const float* dout, const float* inp, int n, int h, int w, int c,
+                   const float* flow, float* dinp, float* dflow, const float* dflow_add,
+                   int ld_add, int convention, void* stream) {
+  OF_CHECK_ARG(convention == OF_WARP_REFERENCE || convention == OF_WARP_IMAGE,
+               "warp bwd: unknown warp convention");
+  return convention == OF_WARP_IMAGE
+             ? warp_bwd_impl<WARP_CV_IMAGE>(dout, inp, n, h, w, c, flow, dinp, dflow, 0, stream,
+                                            dflow_add, ld_add)
+             : warp_bwd_impl<WARP_CV_REFERENCE>(dout, inp, n, h, w, c, flow, dinp, dflow, 0,
+                                                stream, dflow_add, ld_add);
 }
 
 int of_warp_bwd_add(const float* dout, const float* inp, int n, int h, int w, int c,
                     const float* flow, float* dinp, float* dflow, const float* dflow_add,
                     int ld_add, void* stream) {
   OF_CHECK_ARG(dflow_add, "warp bwd add: NULL dflow_add");
-  return warp_bwd_impl(dout, inp, n, h, w, c, flow, dinp, dflow, 0, stream, dflow_add, ld_add);
+  return of_warp_bwd_cv(dout, inp, n, h, w, c, flow, dinp, dflow, dflow_add, ld_add,
+                        OF_WARP_REFERENCE, stream);
 }
 
 int of_bilinear_bwd(const float* dout, const float* inp, int n, int h, int w, int c,
                     const float* pts, float* dinp, float* dpts, void* stream) {
-  return warp_bwd_impl(dout, inp, n, h, w, c, pts, dinp, dpts, 1, stream);
+  return warp_bwd_impl<WARP_CV_REFERENCE>(dout, inp, n, h, w, c, pts, dinp, dpts, 1, stream);
 }
 
 int of_upscale2x_fwd(const float* in, int n, int h, int w, int c, float scale, float* out,
@@ -2251,6 +2292,15 @@ int of_pyramid6(const float* batch, int n, int h, int w, int levels, float* cons
 int of_photo_l1_fwd_multi(const float* const* img6s, const float* const* flows, int n,
                           const int* hs, const int* ws, int levels, float* partials,
                           void* stream) {
+  return of_photo_l1_fwd_multi_cv(img6s, flows, n, hs, ws, levels, partials, OF_WARP_REFERENCE,
+                                  stream);
+}
+
+int of_photo_l1_fwd_multi_cv(const float* const* img6s, const float* const* flows, int n,
+                             const int* hs, const int* ws, int levels, float* partials,
+                             int convention, void* stream) {
+  OF_CHECK_ARG(convention == OF_WARP_REFERENCE || convention == OF_WARP_IMAGE,
+               "photo l1 fwd multi: unknown warp convention");
   OF_CHECK_ARG(img6s && flows && hs && ws && partials && levels >= 1 && levels <= 8,
                "photo l1 fwd multi: args");
   PhotoMulti m{};
@@ -2264,8 +2314,10 @@ int of_photo_l1_fwd_multi(const float* const* img6s, const float* const* flows, 
     m.w[l] = ws[l];
     m.beg[l + 1] = m.beg[l] + of_photo_l1_partials(n, hs[l], ws[l]);
   }
-  hipLaunchKernelGGL(photo_l1_fwd_multi, dim3((unsigned)m.beg[levels]), dim3(PL_THREADS), 0,
-                     as_stream(stream), n, m, partials);
+  hipLaunchKernelGGL(convention == OF_WARP_IMAGE ? photo_l1_fwd_multi<WARP_CV_IMAGE>
+                                                 : photo_l1_fwd_multi<WARP_CV_REFERENCE>,
+                     dim3((unsigned)m.beg[levels]), dim3(PL_THREADS), 0, as_stream(stream), n, m,
+                     partials);
   return check_launch("photo_l1_fwd_multi");
 }
 
@@ -2273,6 +2325,16 @@ int of_photo_l1_bwd_multi(const float* const* img6s, const float* const* flows, 
                           const int* hs, const int* ws, int levels, const float* coefs,
                           const float* dloss, float* const* dflows, const int* lds,
                           void* stream) {
+  return of_photo_l1_bwd_multi_cv(img6s, flows, n, hs, ws, levels, coefs, dloss, dflows, lds,
+                                  OF_WARP_REFERENCE, stream);
+}
+
+int of_photo_l1_bwd_multi_cv(const float* const* img6s, const float* const* flows, int n,
+                             const int* hs, const int* ws, int levels, const float* coefs,
+                             const float* dloss, float* const* dflows, const int* lds,
+                             int convention, void* stream) {
+  OF_CHECK_ARG(convention == OF_WARP_REFERENCE || convention == OF_WARP_IMAGE,
+               "photo l1 bwd multi: unknown warp convention");
   OF_CHECK_ARG(img6s && flows && hs && ws && coefs && dflows && lds && levels >= 1 && levels <= 8,
                "photo l1 bwd multi: args");
   PhotoMulti m{};
@@ -2289,8 +2351,9 @@ int of_photo_l1_bwd_multi(const float* const* img6s, const float* const* flows, 
     m.w[l] = ws[l];
     m.beg[l + 1] = m.beg[l] + (int64_t)n * hs[l] * ws[l];
   }
-  hipLaunchKernelGGL(photo_l1_bwd_multi, dim3(grid_for(m.beg[levels])), dim3(256), 0,
-                     as_stream(stream), n, m, dloss);
+  hipLaunchKernelGGL(convention == OF_WARP_IMAGE ? photo_l1_bwd_multi<WARP_CV_IMAGE>
+                                                 : photo_l1_bwd_multi<WARP_CV_REFERENCE>,
+                     dim3(grid_for(m.beg[levels])), dim3(256), 0, as_stream(stream), n, m, dloss);
   return check_launch("photo_l1_bwd_multi");
 }
 

@@ -30,9 +30,17 @@
 //      then a fixed DPP row reduction), plus the optional addend of of_warp_bwd_add -- in
 //      own_window (its loads issued before the window's), or its own kernel.
 //
+//   The image convention (template parameter CV = WARP_CV_IMAGE, warp_tap.h: column x = j + f0,
+//     row y = i + f1; of_warp_bwd_det_cv): mode A only, as a window around the destination's
+//     OWN position -- every (source, corner) entry lies within R of its source in both axes,
+//     so destination (r, x) scans rows r +- R, columns x +- R, clipped: complete on borders
+//     and corners, with no far-edge extension, no piles and nothing left out of the tiles but
+//     the bins that overflow.  Above key 28 the fixed-point path serves (no mode B).
+//
 // Bitwise reproducible run to run, in eager mode and inside a captured graph alike (the mode,
 // the windows and the path are functions of the flow and dout).
 #include "common.h"
+#include "warp_tap.h"
 
 namespace oflow {
 
@@ -45,11 +53,13 @@ struct DetCorners {
 
 // transformations.py:98-125 with the reference's transposed grid (model.py:65-71, P1): the
 // sample of pixel (i, j) is column x = i + f0, row y = j + f1 (absolute: x = f0, y = f1).
+// CV = WARP_CV_IMAGE (warp_tap.h): column x = j + f0, row y = i + f1.
+template <int CV>
 __device__ __forceinline__ DetCorners det_corners(int i, int j, float f0, float f1, int h, int w,
                                                   bool absolute) {
   DetCorners t;
-  const float x = absolute ? f0 : (float)i + f0;
-  const float y = absolute ? f1 : (float)j + f1;
+  const float x = absolute ? f0 : (float)(CV == WARP_CV_IMAGE ? j : i) + f0;
+  const float y = absolute ? f1 : (float)(CV == WARP_CV_IMAGE ? i : j) + f1;
   const int xi = (int)fmaxf(fminf(floorf(x), 2147483520.f), -2147483520.f);
   const int yi = (int)fmaxf(fminf(floorf(y), 2147483520.f), -2147483520.f);
   const int x0 = min(max(xi, 0), w - 1), x1 = min(max(xi + 1, 0), w - 1);
@@ -208,6 +218,7 @@ __device__ __forceinline__ int fix_shift(const int* __restrict__ hdr, int lg4n) 
   return 61 - e - lg4n;
 }
 
+template <int CV>
 __global__ __launch_bounds__(64 * FX_WAVES) void fix_scatter(const float* __restrict__ dout,
                                                              const float* __restrict__ flow,
                                                              int n, int h, int w, int c,
@@ -242,7 +253,7 @@ __global__ __launch_bounds__(64 * FX_WAVES) void fix_scatter(const float* __rest
       if (i >= h || j >= w) continue;                  // wave-uniform
       const int64_t p = img + (int64_t)i * w + j;
       const float2 f = *reinterpret_cast<const float2*>(flow + 2 * p);
-      const DetCorners t = det_corners(i, j, f.x, f.y, h, w, absolute != 0);
+      const DetCorners t = det_corners<CV>(i, j, f.x, f.y, h, w, absolute != 0);
       const float g = eok ? dout[p * c + e] : 0.f;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -317,6 +328,7 @@ struct DetTaps {
   int64_t off[4];
   float a, bq;
 };
+template <int CV>
 __device__ __forceinline__ DetTaps det_taps(const float* __restrict__ flow, int64_t pp, int h,
                                             int w, int c, int absolute) {
   const int j = (int)(pp % w);
@@ -324,7 +336,7 @@ __device__ __forceinline__ DetTaps det_taps(const float* __restrict__ flow, int6
   const int i = (int)(t2 % h);
   const int64_t img = (t2 / h) * h * w;
   const float2 f = *reinterpret_cast<const float2*>(flow + 2 * pp);
-  const DetCorners t = det_corners(i, j, f.x, f.y, h, w, absolute != 0);
+  const DetCorners t = det_corners<CV>(i, j, f.x, f.y, h, w, absolute != 0);
   DetTaps T;
 #pragma unroll
   for (int k = 0; k < 4; ++k) T.off[k] = (img + (int64_t)t.y[k] * w + t.x[k]) * c;
@@ -334,6 +346,7 @@ __device__ __forceinline__ DetTaps det_taps(const float* __restrict__ flow, int6
 }
 
 // Every lane of the wave calls it (the row reduction reads all 16 lanes).
+template <int CV>
 __device__ __forceinline__ void det_dflow_quads(const float* __restrict__ dout,
                                                 const float* __restrict__ inp, int64_t npix,
                                                 int h, int w, int c,
@@ -343,7 +356,7 @@ __device__ __forceinline__ void det_dflow_quads(const float* __restrict__ dout,
                                                 int64_t p, int q) {
   const bool ok = p < npix;
   const int64_t pp = ok ? p : npix - 1;
-  const DetTaps T = det_taps(flow, pp, h, w, c, absolute);
+  const DetTaps T = det_taps<CV>(flow, pp, h, w, c, absolute);
   float gx = 0.f, gy = 0.f;
   for (int cq = 4 * q; cq < c; cq += 64) {
     const float4 g = *reinterpret_cast<const float4*>(dout + pp * c + cq);
@@ -356,14 +369,15 @@ __device__ __forceinline__ void det_dflow_quads(const float* __restrict__ dout,
   dflow_store(gx, gy, p, ok, q, dflow, dfa, ldfa);
 }
 
+template <int CV>
 __global__ __launch_bounds__(256) void det_dflow_vec(const float* __restrict__ dout,
                                                      const float* __restrict__ inp, int n, int h,
                                                      int w, int c, const float* __restrict__ flow,
                                                      int absolute, float* __restrict__ dflow,
                                                      const float* __restrict__ dfa, int ldfa) {
   const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  det_dflow_quads(dout, inp, (int64_t)n * h * w, h, w, c, flow, absolute, dflow, dfa, ldfa,
-                  gid >> 4, (int)(gid & 15));
+  det_dflow_quads<CV>(dout, inp, (int64_t)n * h * w, h, w, c, flow, absolute, dflow, dfa, ldfa,
+                      gid >> 4, (int)(gid & 15));
 }
 
 // The window gather.  win_accumulate sums a contiguous range of a destination's candidates,
@@ -389,7 +403,7 @@ struct WinDest {
   int k0, k1;                   // the range this group sums
 };
 
-template <bool VEC, int NCB>
+template <bool VEC, int NCB, int CV>
 __device__ __forceinline__ void win_accumulate(float4 (&acc)[NCB], int& found, const WinDest& D,
                                                const float* __restrict__ dimg,
                                                const float* __restrict__ fimg, int h, int w,
@@ -472,11 +486,12 @@ __device__ __forceinline__ void win_accumulate(float4 (&acc)[NCB], int& found, c
       // Interior destination: a candidate hits only if its sample lies in [x - 1, x + 1) x
       // [r - 1, r + 1) (its unclamped corners floor(.) and floor(.) + 1; a clamped corner lands
       // on the border), the same float sums det_corners forms: most lanes skip the corners.
+      const int gx = CV == WARP_CV_IMAGE ? cj[u] : ci[u], gy = CV == WARP_CV_IMAGE ? ci[u] : cj[u];
       const bool maybe =
-          !interior || ((float)ci[u] + f[u].x >= (float)(D.x - 1) && (float)ci[u] + f[u].x < (float)(D.x + 1) &&
-                        (float)cj[u] + f[u].y >= (float)(D.r - 1) && (float)cj[u] + f[u].y < (float)(D.r + 1));
+          !interior || ((float)gx + f[u].x >= (float)(D.x - 1) && (float)gx + f[u].x < (float)(D.x + 1) &&
+                        (float)gy + f[u].y >= (float)(D.r - 1) && (float)gy + f[u].y < (float)(D.r + 1));
       if (ci[u] >= 0 && maybe) {
-        const DetCorners tc = det_corners(ci[u], cj[u], f[u].x, f[u].y, h, w, false);
+        const DetCorners tc = det_corners<CV>(ci[u], cj[u], f[u].x, f[u].y, h, w, false);
 #pragma unroll
         for (int k = 0; k < 4; ++k) m |= (tc.y[k] == D.r && tc.x[k] == D.x) ? 1u << k : 0u;
         ca = tc.a;
@@ -514,10 +529,24 @@ __device__ __forceinline__ void win_accumulate(float4 (&acc)[NCB], int& found, c
 }
 
 // Mode A: the candidates of destination (r, x) for radius R (sources within R of the
-// transposed position; the last row / column to the far edge).
+// transposed position; the last row / column to the far edge).  In the image convention a
+// (source, corner) entry lies within R of its source in both axes -- unclipped within
+// |flow| + 1 <= R - 1, and clipping into the image, which holds the source, only moves it
+// closer -- so the window is rows r +- R, columns x +- R, clipped: complete on borders and
+// corners too, with no far-edge extension.
+template <int CV>
 __device__ __forceinline__ WinDest win_dest_a(int r, int x, int h, int w, int R) {
   WinDest D;
   D.r = r, D.x = x;
+  if (CV == WARP_CV_IMAGE) {
+    D.ilo = max(0, r - R);
+    const int ihi = min(h - 1, r + R);
+    D.jlo = max(0, x - R);
+    D.nj = min(w - 1, x + R) - D.jlo + 1;
+    D.k0 = 0;
+    D.k1 = (ihi - D.ilo + 1) * D.nj;
+    return D;
+  }
   D.ilo = max(0, x - R);
   const int ihi = x == w - 1 ? h - 1 : min(h - 1, x + R);
   D.jlo = max(0, r - R);
@@ -584,10 +613,14 @@ __device__ __forceinline__ bool win_piled(bool mode_a, int r, int x, int h, int 
 // from any distance; piles among them) and bins beyond TILE_CAP entries (appended to olist,
 // count at hdr[0]) -- are left to own_window's rest pass (tiled = 2).  d(flow) of every
 // pixel of the tile as a source (VEC).  Returns at once unless mode A.
+// CV = WARP_CV_IMAGE: the sources of the tile's window are rows r0 - R .. r0 + 3 + R, columns
+// x0 - R .. x0 + 3 + R (win_dest_a), every destination of the image is binned -- no edge or pile
+// is left out -- and only the bins beyond TILE_CAP entries (borders under outward flow, a
+// point many flows converge on) go to the rest pass.
 #ifndef OWN_TILE_WPE
 #define OWN_TILE_WPE 8    // waves per SIMD the registers are sized for (8: two per CU more)
 #endif
-template <bool VEC, int NCB>
+template <bool VEC, int NCB, int CV>
 __global__ __launch_bounds__(256, OWN_TILE_WPE) void own_tile(const float* __restrict__ dout,
                                                              const float* __restrict__ inp,
                                                              const float* __restrict__ flow,
@@ -618,24 +651,26 @@ __global__ __launch_bounds__(256, OWN_TILE_WPE) void own_tile(const float* __res
   const float* fimg = flow + 2 * img;
   const int r = r0 + (grp >> 2), x = x0 + (grp & 3);
   const bool dlive = r < h && x < w;
-  const bool edge = x == w - 1 || r == h - 1;
+  constexpr bool IMG = CV == WARP_CV_IMAGE;
+  const bool edge = !IMG && (x == w - 1 || r == h - 1);
   const int64_t pix = dlive ? img + (int64_t)r * w + x : npix - 1;
   if (threadIdx.x < 16) t_cnt[threadIdx.x] = 0;
   __syncthreads();
-  const int ilo = max(0, x0 - R), ihi = min(h - 1, x0 + 3 + R);
-  const int jlo = max(0, r0 - R), jhi = min(w - 1, r0 + 3 + R);
+  const int ic = IMG ? r0 : x0, jc = IMG ? x0 : r0;    // the window's centre tile, as sources
+  const int ilo = max(0, ic - R), ihi = min(h - 1, ic + 3 + R);
+  const int jlo = max(0, jc - R), jhi = min(w - 1, jc + 3 + R);
   const int nsj = jhi - jlo + 1;
   const int nsrc = ihi >= ilo && nsj > 0 ? (ihi - ilo + 1) * nsj : 0;
   for (int e = threadIdx.x; e < nsrc; e += 256) {
     const int i = ilo + e / nsj, j = jlo + e % nsj;
     const float2 f = *reinterpret_cast<const float2*>(fimg + 2 * ((int64_t)i * w + j));
-    const DetCorners tc = det_corners(i, j, f.x, f.y, h, w, false);
+    const DetCorners tc = det_corners<CV>(i, j, f.x, f.y, h, w, false);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int yr = tc.y[k] - r0, xr = tc.x[k] - x0;
       if ((unsigned)yr < 4u && (unsigned)xr < 4u) {
         const int g = yr * 4 + xr;
-        if (r0 + yr == h - 1 || x0 + xr == w - 1) continue;   // edge / pile: the rest pass
+        if (!IMG && (r0 + yr == h - 1 || x0 + xr == w - 1)) continue;   // edge / pile: the rest pass
         const int pos = atomicAdd(&t_cnt[g], 1);
         if (pos < TILE_CAP) {
           b_off[g][pos] = 4 * (i * w + j) + k;                  // the code
@@ -705,7 +740,7 @@ __global__ __launch_bounds__(256, OWN_TILE_WPE) void own_tile(const float* __res
     }
   }
   if (VEC)                   // d(flow) of this pixel as a source (every lane of the wave)
-    det_dflow_quads(dout, inp, npix, h, w, c, flow, 0, dflow, dfa, ldfa, dlive ? pix : npix, q);
+    det_dflow_quads<CV>(dout, inp, npix, h, w, c, flow, 0, dflow, dfa, ldfa, dlive ? pix : npix, q);
 }
 
 // The window kernel (launched when rmax >= 0).  Blocks [0, n * npb): one workgroup per pile
@@ -716,7 +751,10 @@ __global__ __launch_bounds__(256, OWN_TILE_WPE) void own_tile(const float* __res
 // a source, its loads issued before the window's (DFQ quads per lane).  A window that does
 // not serve (mode B, a count short of 4 n h w) is overwritten by the fixed-point path; with
 // neither mode (R > rmax and V > WIN_VMAX) the kernel forms d(flow) only.
-template <bool VEC, int NCB, bool TPRE = false>
+// CV = WARP_CV_IMAGE: mode A only (no piles, no pile blocks: the host launches none; the rest
+// pass is the overflow list alone); above key 28 the kernel forms d(flow) and the fixed-point
+// path serves -- an image-convention mode B is not built.
+template <bool VEC, int NCB, bool TPRE = false, int CV = WARP_CV_REFERENCE>
 __global__ __launch_bounds__(256) void own_window(const float* __restrict__ dout,
                                                   const float* __restrict__ inp,
                                                   const float* __restrict__ flow, int n, int h,
@@ -738,24 +776,25 @@ __global__ __launch_bounds__(256) void own_window(const float* __restrict__ dout
   const int nq = VEC ? c >> 2 : c;
   const int R = det_R(hdr);
   const bool mode_a = R <= rmax;                       // uniform over the grid
-  const bool mode_b = !mode_a && (det_bank_max(hdr, DET_ROUGH) <= WIN_VMAX || rmax == 1);
-  const int npb = h >= 2 && w >= 2 ? 2 * w + 2 * (h - 2) : 0;
+  constexpr bool IMG = CV == WARP_CV_IMAGE;
+  const bool mode_b = !IMG && !mode_a && (det_bank_max(hdr, DET_ROUGH) <= WIN_VMAX || rmax == 1);
+  const int npb = !IMG && h >= 2 && w >= 2 ? 2 * w + 2 * (h - 2) : 0;
   const int npile = n * npb;
   int found = 0;
-  if ((int)blockIdx.x < npile) {
+  if (!IMG && (int)blockIdx.x < npile) {
     int r, x;
-    const int img_i = blockIdx.x / npb;
-    win_pile_dest(blockIdx.x % npb, h, w, r, x);
+    const int img_i = blockIdx.x / max(npb, 1);
+    win_pile_dest(blockIdx.x % max(npb, 1), h, w, r, x);
     if (!(mode_a || mode_b) || !win_piled(mode_a, r, x, h, w)) return;   // (block-uniform)
     const int64_t img = (int64_t)img_i * hw;
-    WinDest D = mode_a ? win_dest_a(r, x, h, w, R) : win_dest_b(flow + 2 * img, r, x, h, w, R);
+    WinDest D = mode_a ? win_dest_a<CV>(r, x, h, w, R) : win_dest_b(flow + 2 * img, r, x, h, w, R);
     const int seg = (D.k1 + 15) / 16;
     D.k0 = min(grp * seg, D.k1);
     D.k1 = min(D.k0 + seg, D.k1);
     for (int cb0 = 0; cb0 < nq; cb0 += 16 * NCB) {
       float4 acc[NCB];
       int fnd = 0;
-      win_accumulate<VEC, NCB>(acc, fnd, D, dout + img * c, flow + 2 * img, h, w, c, cb0,
+      win_accumulate<VEC, NCB, CV>(acc, fnd, D, dout + img * c, flow + 2 * img, h, w, c, cb0,
                                l_off[grp], l_w[grp], q, src0);
       if (cb0 == 0) found = fnd;
 #pragma unroll
@@ -791,8 +830,8 @@ __global__ __launch_bounds__(256) void own_window(const float* __restrict__ dout
     // and column of every image (piles excepted: the blocks above) and for the destinations
     // whose bins overflowed (olist, hdr[0] of them), 16 a block, grid-stride; own_tile formed
     // d(flow)
-    const int per = w + h - 1;
-    const int64_t nedge = (int64_t)n * per;
+    const int per = w + h - 1;                          // (the image convention: no edge rest)
+    const int64_t nedge = IMG ? 0 : (int64_t)n * per;
     const int64_t total = nedge + hdr[0];
     const int64_t nb = (int64_t)gridDim.x - npile;
     for (int64_t e0 = ((int64_t)blockIdx.x - npile) * 16; e0 < total; e0 += nb * 16) {
@@ -807,13 +846,13 @@ __global__ __launch_bounds__(256) void own_window(const float* __restrict__ dout
       }
       const int64_t img = (pix / hw) * hw;
       const int r = (int)((pix - img) / w), x = (int)((pix - img) % w);
-      const bool go = live && !win_piled(true, r, x, h, w);
-      WinDest D = win_dest_a(r, x, h, w, R);
+      const bool go = live && (IMG || !win_piled(true, r, x, h, w));
+      WinDest D = win_dest_a<CV>(r, x, h, w, R);
       if (!go) D.k1 = 0;
       for (int cb0 = 0; cb0 < nq; cb0 += 16 * NCB) {
         float4 acc[NCB];
         int fnd = 0;
-        win_accumulate<VEC, NCB>(acc, fnd, D, dout + img * c, flow + 2 * img, h, w, c, cb0,
+        win_accumulate<VEC, NCB, CV>(acc, fnd, D, dout + img * c, flow + 2 * img, h, w, c, cb0,
                                  l_off[grp], l_w[grp], q, src0);
         if (go) {
 #pragma unroll
@@ -847,8 +886,8 @@ __global__ __launch_bounds__(256) void own_window(const float* __restrict__ dout
     const float* fimg = flow + 2 * img;
     const int r = r0 + (grp >> 2), x = x0 + (grp & 3);
     const bool dlive = r < h && x < w;
-    const bool piled = dlive && win_piled(true, r, x, h, w);
-    const bool edge = x == w - 1 || r == h - 1;
+    const bool piled = !IMG && dlive && win_piled(true, r, x, h, w);
+    const bool edge = !IMG && (x == w - 1 || r == h - 1);
     const int64_t pix = dlive ? img + (int64_t)r * w + x : npix - 1;
     // TPRE (of_set_tuning key 35): d(flow)'s loads of this pixel issued now, consumed at the
     // end -- in flight across the binning and the gather
@@ -857,7 +896,7 @@ __global__ __launch_bounds__(256) void own_window(const float* __restrict__ dout
     DetTaps T{};
     const bool pre = kPre && c <= 64 * NCB;
     if (kPre && pre) {
-      T = det_taps(flow, pix, h, w, c, 0);
+      T = det_taps<CV>(flow, pix, h, w, c, 0);
 #pragma unroll
       for (int b = 0; b < (kPre ? NCB : 1); ++b) {
         const int cq = 4 * q + 64 * b;
@@ -871,22 +910,24 @@ __global__ __launch_bounds__(256) void own_window(const float* __restrict__ dout
     }
     if (threadIdx.x < 16) t_cnt[threadIdx.x] = 0;
     __syncthreads();
-    // the sources: i in [x0 - R, x0 + 3 + R], j in [r0 - R, r0 + 3 + R] (clipped)
-    const int ilo = max(0, x0 - R), ihi = min(h - 1, x0 + 3 + R);
-    const int jlo = max(0, r0 - R), jhi = min(w - 1, r0 + 3 + R);
+    // the sources: i in [x0 - R, x0 + 3 + R], j in [r0 - R, r0 + 3 + R] (clipped); in the
+    // image convention i around r0, j around x0
+    const int ic = IMG ? r0 : x0, jc = IMG ? x0 : r0;
+    const int ilo = max(0, ic - R), ihi = min(h - 1, ic + 3 + R);
+    const int jlo = max(0, jc - R), jhi = min(w - 1, jc + 3 + R);
     const int nsj = jhi - jlo + 1;
     const int nsrc = ihi >= ilo && nsj > 0 ? (ihi - ilo + 1) * nsj : 0;
     for (int e = threadIdx.x; e < nsrc; e += 256) {
       const int i = ilo + e / nsj, j = jlo + e % nsj;
       const float2 f = *reinterpret_cast<const float2*>(fimg + 2 * ((int64_t)i * w + j));
-      const DetCorners tc = det_corners(i, j, f.x, f.y, h, w, false);
+      const DetCorners tc = det_corners<CV>(i, j, f.x, f.y, h, w, false);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int yr = tc.y[k] - r0, xr = tc.x[k] - x0;
         if ((unsigned)yr < 4u && (unsigned)xr < 4u) {
           const int g = yr * 4 + xr;
           const int rr = r0 + yr, xx = x0 + xr;
-          if (rr == h - 1 || xx == w - 1) continue;       // edge / pile: not binned
+          if (!IMG && (rr == h - 1 || xx == w - 1)) continue;   // edge / pile: not binned
           const int pos = atomicAdd(&t_cnt[g], 1);
           if (pos < WIN_CAP) {
             l_off[g][pos] = 4 * (i * w + j) + k;          // the code (< 2^31: 4 n h w checked)
@@ -901,12 +942,12 @@ __global__ __launch_bounds__(256) void own_window(const float* __restrict__ dout
     // the scan fallback (wave-wide shuffles inside: all four groups of the wave call it when
     // any of them needs it, the others with an empty range)
     if (__ballot(scan && q == 0) != 0) {
-      WinDest D = win_dest_a(dlive ? r : 0, dlive ? x : 0, h, w, R);
+      WinDest D = win_dest_a<CV>(dlive ? r : 0, dlive ? x : 0, h, w, R);
       if (!scan) D.k1 = 0;
       for (int cb0 = 0; cb0 < nq; cb0 += 16 * NCB) {
         float4 acc[NCB];
         int fnd = 0;
-        win_accumulate<VEC, NCB>(acc, fnd, D, dout + img * c, fimg, h, w, c, cb0,
+        win_accumulate<VEC, NCB, CV>(acc, fnd, D, dout + img * c, fimg, h, w, c, cb0,
                                  l_off[grp], l_w[grp], q, src0);
         if (scan) {
 #pragma unroll
@@ -981,8 +1022,8 @@ __global__ __launch_bounds__(256) void own_window(const float* __restrict__ dout
         if (4 * q + 64 * b < c) dflow_quad(gx, gy, T.a, T.bq, pg[b], pP[0][b], pP[1][b], pP[2][b], pP[3][b]);
       dflow_store(gx, gy, dlive ? pix : npix, dlive, q, dflow, dfa, ldfa);
     } else if (VEC) {          // d(flow) of this pixel as a source (every lane of the wave)
-      det_dflow_quads(dout, inp, npix, h, w, c, flow, 0, dflow, dfa, ldfa,
-                      dlive ? img + (int64_t)r * w + x : npix, q);
+      det_dflow_quads<CV>(dout, inp, npix, h, w, c, flow, 0, dflow, dfa, ldfa,
+                          dlive ? img + (int64_t)r * w + x : npix, q);
     }
     return;
   }
@@ -998,7 +1039,7 @@ __global__ __launch_bounds__(256) void own_window(const float* __restrict__ dout
   float4 pg[DFQ], pP[4][DFQ];
   DetTaps T;
   if (pre) {
-    T = det_taps(flow, dd, h, w, c, 0);
+    T = det_taps<CV>(flow, dd, h, w, c, 0);
 #pragma unroll
     for (int b = 0; b < DFQ; ++b) {
       const int cq = 4 * q + 64 * b;
@@ -1017,13 +1058,13 @@ __global__ __launch_bounds__(256) void own_window(const float* __restrict__ dout
     const int64_t img = dd / hw * hw;
     const int rem = (int)(dd - img);
     const int r = rem / w, x = rem % w;
-    const bool skip = !live || win_piled(mode_a, r, x, h, w);
-    WinDest D = mode_a ? win_dest_a(r, x, h, w, R) : win_dest_b(flow + 2 * img, r, x, h, w, R);
+    const bool skip = !live || (!IMG && win_piled(mode_a, r, x, h, w));
+    WinDest D = mode_a ? win_dest_a<CV>(r, x, h, w, R) : win_dest_b(flow + 2 * img, r, x, h, w, R);
     if (skip) D.k1 = 0;
     for (int cb0 = 0; cb0 < nq; cb0 += 16 * NCB) {     // every lane runs every iteration
       float4 acc[NCB];
       int fnd = 0;
-      win_accumulate<VEC, NCB>(acc, fnd, D, dout + img * c, flow + 2 * img, h, w, c, cb0,
+      win_accumulate<VEC, NCB, CV>(acc, fnd, D, dout + img * c, flow + 2 * img, h, w, c, cb0,
                                l_off[grp], l_w[grp], q, src0);
       if (cb0 == 0) found = fnd;
       if (!skip) {
@@ -1051,10 +1092,11 @@ __global__ __launch_bounds__(256) void own_window(const float* __restrict__ dout
   } else
 #endif
   if (VEC) {
-    det_dflow_quads(dout, inp, npix, h, w, c, flow, 0, dflow, dfa, ldfa, d, q);
+    det_dflow_quads<CV>(dout, inp, npix, h, w, c, flow, 0, dflow, dfa, ldfa, d, q);
   }
 }
 
+template <int CV>
 __global__ __launch_bounds__(256) void det_dflow_scalar(const float* __restrict__ dout,
                                                         const float* __restrict__ inp, int n,
                                                         int h, int w, int c,
@@ -1068,7 +1110,7 @@ __global__ __launch_bounds__(256) void det_dflow_scalar(const float* __restrict_
   const int64_t t2 = p / w;
   const int i = (int)(t2 % h);
   const int64_t img = (t2 / h) * h * w;
-  const DetCorners t = det_corners(i, j, flow[2 * p], flow[2 * p + 1], h, w, absolute != 0);
+  const DetCorners t = det_corners<CV>(i, j, flow[2 * p], flow[2 * p + 1], h, w, absolute != 0);
   const float a = t.a, bq = t.b;
   float gx = 0.f, gy = 0.f;
   for (int e = 0; e < c; ++e) {
@@ -1126,9 +1168,14 @@ size_t of_warp_bwd_det_header(int n, int h, int w, int c) {
   return L.hdr;
 }
 
-int of_warp_bwd_det(const float* dout, const float* inp, int n, int h, int w, int c,
-                    const float* flow, int absolute, float* dinp, float* dflow,
-                    const float* dflow_add, int ld_add, void* ws, size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+
+template <int CV>
+int det_impl(const float* dout, const float* inp, int n, int h, int w, int c, const float* flow,
+             int absolute, float* dinp, float* dflow, const float* dflow_add, int ld_add,
+             void* ws, size_t ws_bytes, void* stream) {
   OF_CHECK_ARG(dout && inp && flow && dflow, "warp bwd det: NULL pointer");
   OF_CHECK_ARG(n > 0 && h > 0 && w > 0 && c > 0, "warp bwd det: dims");
   OF_CHECK_ARG(!dflow_add || ld_add >= 2, "warp bwd det: ld of the added flow gradient");
@@ -1141,10 +1188,10 @@ int of_warp_bwd_det(const float* dout, const float* inp, int n, int h, int w, in
   const dim3 gp((unsigned)cdiv(npix, 256));
   if (!dinp) {
     if (vec)
-      hipLaunchKernelGGL(det_dflow_vec, gq, dim3(256), 0, s, dout, inp, n, h, w, c, flow,
+      hipLaunchKernelGGL(det_dflow_vec<CV>, gq, dim3(256), 0, s, dout, inp, n, h, w, c, flow,
                          absolute, dflow, dflow_add, ld_add);
     else
-      hipLaunchKernelGGL(det_dflow_scalar, gp, dim3(256), 0, s, dout, inp, n, h, w, c, flow,
+      hipLaunchKernelGGL(det_dflow_scalar<CV>, gp, dim3(256), 0, s, dout, inp, n, h, w, c, flow,
                          absolute, dflow, dflow_add, ld_add);
     return check_launch("warp_bwd_det: dflow");
   }
@@ -1163,17 +1210,19 @@ int of_warp_bwd_det(const float* dout, const float* inp, int n, int h, int w, in
     const unsigned gr = (unsigned)std::min<int64_t>(cdiv(npix, 256), 4 * device_cus());
     hipLaunchKernelGGL(own_radius, dim3(gr), dim3(256), 0, s, flow, npix, h, w, hdr);
     const int nq = vec ? c / 4 : c;
-    auto kw = vec ? (g_det_tpre ? (nq > 16 ? own_window<true, 2, true> : own_window<true, 1, true>)
-                                : (nq > 16 ? own_window<true, 2> : own_window<true, 1>))
-                  : (nq > 16 ? own_window<false, 2> : own_window<false, 1>);
-    const int64_t npile = h >= 2 && w >= 2 ? (int64_t)n * (2 * w + 2 * (h - 2)) : 0;
+    auto kw = vec ? (g_det_tpre ? (nq > 16 ? own_window<true, 2, true, CV> : own_window<true, 1, true, CV>)
+                                : (nq > 16 ? own_window<true, 2, false, CV> : own_window<true, 1, false, CV>))
+                  : (nq > 16 ? own_window<false, 2, false, CV> : own_window<false, 1, false, CV>);
+    // (the image convention has no piles: own_window counts no pile blocks either)
+    const int64_t npile =
+        CV != WARP_CV_IMAGE && h >= 2 && w >= 2 ? (int64_t)n * (2 * w + 2 * (h - 2)) : 0;
     const int64_t ntile = g_det_tile ? (int64_t)n * ((h + 3) / 4) * ((w + 3) / 4) : 0;
     // key 34 = 2: own_tile first (mode A's interior destinations), the rest in own_window; the
     // overflow list lives in the fixed-point accumulator's space (unused in mode A)
     int* olist = reinterpret_cast<int*>(base + L.acc);
     if (g_det_tile == 2) {
-      auto kt = vec ? (nq > 16 ? own_tile<true, 2> : own_tile<true, 1>)
-                    : (nq > 16 ? own_tile<false, 2> : own_tile<false, 1>);
+      auto kt = vec ? (nq > 16 ? own_tile<true, 2, CV> : own_tile<true, 1, CV>)
+                    : (nq > 16 ? own_tile<false, 2, CV> : own_tile<false, 1, CV>);
       hipLaunchKernelGGL(kt, dim3((unsigned)ntile), dim3(256), 0, s, dout, inp, flow, n, h, w, c,
                          hdr, rmax, dinp, dflow, dflow_add, ld_add, olist);
       if (int st = check_launch("warp_bwd_det: tiles")) return st;
@@ -1193,19 +1242,42 @@ int of_warp_bwd_det(const float* dout, const float* inp, int n, int h, int w, in
                      reinterpret_cast<int4*>(acc), (nel + 1) / 2, hdr, rmax, npix);
   const int64_t tiles = (int64_t)n * cdiv(h, FX_T) * cdiv(w, FX_T) * ((c + 63) / 64);
   const unsigned gfx = (unsigned)std::min<int64_t>(tiles, std::min(fxg, 2) * device_cus());   // (grid-stride)
-  hipLaunchKernelGGL(fix_scatter, dim3(gfx), dim3(64 * FX_WAVES), 0, s, dout, flow,
+  hipLaunchKernelGGL(fix_scatter<CV>, dim3(gfx), dim3(64 * FX_WAVES), 0, s, dout, flow,
                      n, h, w, c, absolute, hdr, rmax, lg4n, acc);
   hipLaunchKernelGGL(fix_convert, dim3(gs), dim3(256), 0, s,
                      reinterpret_cast<const long long*>(acc), nel, hdr, rmax, npix, lg4n, dinp);
   if (int st = check_launch("warp_bwd_det: fixed point")) return st;
   if (rmax >= 0 && vec) return OF_OK;                  // d(flow) formed by own_window
   if (vec)
-    hipLaunchKernelGGL(det_dflow_vec, gq, dim3(256), 0, s, dout, inp, n, h, w, c, flow, absolute,
-                       dflow, dflow_add, ld_add);
+    hipLaunchKernelGGL(det_dflow_vec<CV>, gq, dim3(256), 0, s, dout, inp, n, h, w, c, flow,
+                       absolute, dflow, dflow_add, ld_add);
   else
-    hipLaunchKernelGGL(det_dflow_scalar, gp, dim3(256), 0, s, dout, inp, n, h, w, c, flow,
+    hipLaunchKernelGGL(det_dflow_scalar<CV>, gp, dim3(256), 0, s, dout, inp, n, h, w, c, flow,
                        absolute, dflow, dflow_add, ld_add);
   return check_launch("warp_bwd_det: dflow");
+}
+
+}  // namespace
+
+extern "C" {
+
+int of_warp_bwd_det(const float* dout, const float* inp, int n, int h, int w, int c,
+                    const float* flow, int absolute, float* dinp, float* dflow,
+                    const float* dflow_add, int ld_add, void* ws, size_t ws_bytes, void* stream) {
+  return det_impl<WARP_CV_REFERENCE>(dout, inp, n, h, w, c, flow, absolute, dinp, dflow,
+                                     dflow_add, ld_add, ws, ws_bytes, stream);
+}
+
+int of_warp_bwd_det_cv(const float* dout, const float* inp, int n, int h, int w, int c,
+                       const float* flow, float* dinp, float* dflow, const float* dflow_add,
+                       int ld_add, int convention, void* ws, size_t ws_bytes, void* stream) {
+  OF_CHECK_ARG(convention == OF_WARP_REFERENCE || convention == OF_WARP_IMAGE,
+               "warp bwd det: unknown warp convention");
+  return convention == OF_WARP_IMAGE
+             ? det_impl<WARP_CV_IMAGE>(dout, inp, n, h, w, c, flow, 0, dinp, dflow, dflow_add,
+                                       ld_add, ws, ws_bytes, stream)
+             : det_impl<WARP_CV_REFERENCE>(dout, inp, n, h, w, c, flow, 0, dinp, dflow,
+                                           dflow_add, ld_add, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

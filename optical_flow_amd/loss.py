@@ -20,10 +20,18 @@ class LossLayer:
     an illumination-robust data term that compares the local intensity order of image 1 and
     of the warped image 2 in a (2 census_radius + 1)^2 window, averaged over pixels and scales
     (ops.census_loss; DESIGN.md "Census term").  ``photometric_weight`` scales the photometric
-    term; 0 drops it (its kernels are not launched), which needs ``census_weight`` > 0."""
+    term; 0 drops it (its kernels are not launched), which needs ``census_weight`` > 0.
+
+    ``warp_convention`` (build-added): "reference" (default) warps image 2 on the reference's
+    transposed grid (P1); "image" takes the flows as image-coordinate displacements (channel 0
+    along x, channel 1 along y) in the photometric and the census term, so the true motion
+    brings the loss to zero.  It must be the net's (Trainer raises ValueError otherwise)."""
 
     def __init__(self, smoothness_weight=0.0, edge_alpha=0.0, smoothness_eps=1e-4,
-                 census_weight=0.0, census_radius=3, photometric_weight=1.0):
+                 census_weight=0.0, census_radius=3, photometric_weight=1.0,
+                 warp_convention="reference"):
+        ops.warp_convention(warp_convention)
+        self.warp_convention = warp_convention
         if not smoothness_weight >= 0:
             raise ValueError("smoothness_weight must be >= 0, got %r" % (smoothness_weight,))
         if not edge_alpha >= 0:
@@ -57,10 +65,10 @@ class LossLayer:
         assert batch_imgs.shape[3] == 6
         if self.census_weight == 0.0 and self.photometric_weight == 1.0:
             if self.smoothness_weight == 0.0:
-                return ops.photometric_loss(batch_imgs, list(flows))
+                return ops.photometric_loss(batch_imgs, list(flows), self.warp_convention)
             return ops.flow_loss(batch_imgs, list(flows), self.smoothness_weight,
-                                 self.edge_alpha, self.smoothness_eps)
+                                 self.edge_alpha, self.smoothness_eps, self.warp_convention)
         return ops.census_flow_loss(batch_imgs, list(flows), self.census_weight,
                                     self.census_radius, self.photometric_weight,
                                     self.smoothness_weight, self.edge_alpha,
-                                    self.smoothness_eps)
+                                    self.smoothness_eps, self.warp_convention)

@@ -273,14 +273,17 @@ def create_cost_volume(features1, features2, max_disp):
     return ops.cost_volume(features1, features2, max_disp)
 
 
-def warp_features(flow_1_to_2, features2):
+def warp_features(flow_1_to_2, features2, convention="reference"):
     """model.py:55-73 with the reference's index convention (P1): the grid is
-    meshgrid(range(h), range(w), 'ij') + flow, sampled as (x=ch0, y=ch1)."""
+    meshgrid(range(h), range(w), 'ij') + flow, sampled as (x=ch0, y=ch1).
+    ``convention="image"`` (build-added) adds the flow to (column, row) instead, so that
+    channel 0 is an x and channel 1 a y displacement and a zero flow is the identity
+    (ops.warp_convention); unknown names raise ValueError."""
     _, height, width, _ = features2.shape
     assert flow_1_to_2.shape[1] == height
     assert flow_1_to_2.shape[2] == width
     assert flow_1_to_2.shape[3] == 2
-    return ops.warp(features2, flow_1_to_2)
+    return ops.warp(features2, flow_1_to_2, convention)
 
 
 def upscale_flow(flow):
@@ -300,6 +303,7 @@ class FlowHead:
         # (464-byte) row runs the level-3/2 c0 convs 12-15 % slower than a 120-float one in
         # both precisions (profiles/r1_conv_bench*.txt); the zero channels cost 3.5 % MACs.
         self.cp = (self.cin + 7) // 8 * 8
+        self.warp_convention = "reference"      # FlowNet sets its own on every head
         P = store.params
         ver = lambda: store.version
         self.convs = []
@@ -311,13 +315,16 @@ class FlowHead:
                                             name=pre))
 
     def __call__(self, features1, features2, previous_flow):
-        return flow_module(features1, features2, previous_flow, self.max_disp, head=self)
+        return flow_module(features1, features2, previous_flow, self.max_disp, head=self,
+                           convention=self.warp_convention)
 
 
-def flow_module(features1, features2, previous_flow, max_disp, head: Optional[FlowHead] = None):
+def flow_module(features1, features2, previous_flow, max_disp, head: Optional[FlowHead] = None,
+                convention="reference"):
     """model.py:80-116: [upscale + warp] -> cost volume -> concat -> 6 convs.  Keras creates
     new conv layers per call; here ``head`` carries them (a fresh randomly initialised head
-    is created when omitted, mirroring that)."""
+    is created when omitted, mirroring that).  ``convention``: the warp's (warp_features)."""
+    ops.warp_convention(convention)
     assert features1.shape[1] == features2.shape[1]
     assert features1.shape[2] == features2.shape[2]
     assert features1.shape[3] == features2.shape[3]
@@ -335,7 +342,7 @@ def flow_module(features1, features2, previous_flow, max_disp, head: Optional[Fl
         assert previous_flow.shape[2] * 2 == features1.shape[2]
         assert previous_flow.shape[3] == 2
         flow_up = upscale_flow(previous_flow)
-        features2_warped = warp_features(flow_up, features2)
+        features2_warped = warp_features(flow_up, features2, convention)
     else:
         flow_up = None
         features2_warped = features2
@@ -349,10 +356,16 @@ class FlowNet:
     """The Keras ``Model`` returned by build_flow_net (model.py:119-143)."""
 
     def __init__(self, height, width, max_disp=3, seed=0, device="cuda", values=None,
-                 precision="fp32", levels=4, bn_mode="inference"):
+                 precision="fp32", levels=4, bn_mode="inference", warp_convention="reference"):
         """levels=5 enables the reference's commented-out 5th pyramid level (model.py:24-25,
         138, 141): encoder stage 5 (512 channels at H/32) and flow4 at H/2.  bn_mode:
-        "inference" (train.py:51, the default) or "training" (old/train.py:59; P5)."""
+        "inference" (train.py:51, the default) or "training" (old/train.py:59; P5).
+        warp_convention: "reference" (default: the reference's transposed grid, P1) or
+        "image" (flows are image-coordinate displacements), used by the warp of every
+        flow_module; readable as ``net.warp_convention``.  It is not a weight: checkpoints
+        do not record it, and weights trained under one convention mean nothing under the
+        other.  The loss layer must use the same one (Trainer checks)."""
+        ops.warp_convention(warp_convention)
         assert levels in (4, 5), levels
         m = 2 ** levels
         assert height % m == 0 and width % m == 0, \
@@ -363,6 +376,9 @@ class FlowNet:
                                 order=backward_order(max_disp, levels), seed=seed)
         self.encoder = Encoder(self.store, levels=levels, bn_mode=bn_mode)
         self.heads = [FlowHead(self.store, level, max_disp, levels) for level in range(levels)]
+        self.warp_convention = warp_convention
+        for head in self.heads:
+            head.warp_convention = warp_convention
         self.name = "flow_net"
         self._packer = None
         self.set_precision(precision)
@@ -470,13 +486,14 @@ class FlowNet:
 
 
 def build_flow_net(height, width, pretrained_weights_path=None, max_disp=3, seed=0,
-                   device="cuda", precision="fp32", levels=4, bn_mode="inference"):
+                   device="cuda", precision="fp32", levels=4, bn_mode="inference",
+                   warp_convention="reference"):
     """model.py:119-143.  ``pretrained_weights_path``: the stand-alone ResNet18 encoder's
     weights, as a TF checkpoint (Keras object-based keys, checkpoint.py) or an .npz of
     encoder parameter names; like the reference (model.py:128-129) every encoder weight must
     be matched."""
     net = FlowNet(height, width, max_disp, seed=seed, device=device, precision=precision,
-                  levels=levels, bn_mode=bn_mode)
+                  levels=levels, bn_mode=bn_mode, warp_convention=warp_convention)
     if pretrained_weights_path is not None:
         enc_names = [p.name for p in encoder_spec(levels)]
         if (os.path.exists(pretrained_weights_path + ".index")

@@ -1801,13 +1801,38 @@ def corr_concat(f1, f2w, flow_up, max_disp, cp, precision="fp32", layers=None):
 
 
 # ============================================================================ warp =====
+# The warp convention (include/oflow.h, OF_WARP_REFERENCE / OF_WARP_IMAGE): which grid the flow
+# is added to.  "reference" is the reference's transposed grid (x = i + flow0, y = j + flow1:
+# P1), the default everywhere; "image" is image coordinates (x = j + flow0, y = i + flow1), in
+# which flow[..., 0] is the column and flow[..., 1] the row displacement and a zero flow is the
+# identity.  An explicit argument wherever a warp is taken, never global state.
+WARP_CONVENTIONS = {"reference": _lib.WARP_REFERENCE, "image": _lib.WARP_IMAGE}
+
+
+def warp_convention(name) -> int:
+    """The C ABI's code of a convention name; ValueError for anything else."""
+    if not isinstance(name, str) or name not in WARP_CONVENTIONS:
+        raise ValueError("warp convention must be one of %s, got %r"
+                         % (sorted(WARP_CONVENTIONS), name))
+    return WARP_CONVENTIONS[name]
+
+
+def _call_cv(name, cv, *args):
+    """The entry point ``name`` in the reference convention (the call it always was); in the
+    image convention its ``_cv`` form, which takes the convention before the stream."""
+    if cv == _lib.WARP_REFERENCE:
+        return call(name, *args)
+    return call(name + "_cv", *args[:-1], cv, args[-1])
+
+
 class _Warp(torch.autograd.Function):
     """warp_features (model.py:55-73) / bilinear_interpolation (transformations.py:85-129)."""
 
     @staticmethod
-    def forward(ctx, inp, flow, absolute, fa=None):
+    def forward(ctx, inp, flow, absolute, fa=None, cv=0):
         _check_dev(inp, flow)
         ctx.fa = fa
+        ctx.cv = cv
         if fa is not None and flow.requires_grad:
             fa.warp_flow_grad = True
         inp, flow = inp.contiguous(), flow.contiguous()
@@ -1815,8 +1840,10 @@ class _Warp(torch.autograd.Function):
         assert flow.shape == (n, h, w, 2), "flow must be (B, h, w, 2) like features"
         out = torch.empty_like(inp)
         ctx.dst = grad_dst(inp)
-        call("of_bilinear_fwd" if absolute else "of_warp_fwd", _ptr(inp), n, h, w, c,
-             _ptr(flow), _ptr(out), _stream())
+        if absolute:
+            call("of_bilinear_fwd", _ptr(inp), n, h, w, c, _ptr(flow), _ptr(out), _stream())
+        else:
+            _call_cv("of_warp_fwd", cv, _ptr(inp), n, h, w, c, _ptr(flow), _ptr(out), _stream())
         ctx.save_for_backward(inp, flow)
         ctx.absolute = absolute
         return out
@@ -1841,24 +1868,39 @@ class _Warp(torch.autograd.Function):
             wsk, wsp, wsb = _workspace(
                 _lib.lib().of_warp_bwd_det_workspace(n, h, w, c) if dinp is not None else 0,
                 dout.device)
-            call("of_warp_bwd_det", _ptr(dout), _ptr(inp), n, h, w, c, _ptr(flow),
-                 int(ctx.absolute), _ptr(dinp), _ptr(dflow), add, ld, wsp, wsb, s)
-            return dinp, (dflow if ctx.needs_input_grad[1] else None), None, None
+            if ctx.absolute or ctx.cv == _lib.WARP_REFERENCE:
+                call("of_warp_bwd_det", _ptr(dout), _ptr(inp), n, h, w, c, _ptr(flow),
+                     int(ctx.absolute), _ptr(dinp), _ptr(dflow), add, ld, wsp, wsb, s)
+            else:
+                call("of_warp_bwd_det_cv", _ptr(dout), _ptr(inp), n, h, w, c, _ptr(flow),
+                     _ptr(dinp), _ptr(dflow), add, ld, ctx.cv, wsp, wsb, s)
+            return dinp, (dflow if ctx.needs_input_grad[1] else None), None, None, None
         if dinp is not None:
             call("of_fill", _ptr(dinp), 0.0, dinp.numel(), s)
         if fa is not None and fa.addend is not None and ctx.needs_input_grad[1]:
             dcat, off, ld = fa.addend            # the concat's flow slice (FlowAdd)
-            call("of_warp_bwd_add", _ptr(dout), _ptr(inp), n, h, w, c, _ptr(flow), _ptr(dinp),
-                 _ptr(dflow), C.c_void_p(dcat.data_ptr() + 4 * off), ld, s)
+            add = C.c_void_p(dcat.data_ptr() + 4 * off)
+            if ctx.cv == _lib.WARP_REFERENCE:
+                call("of_warp_bwd_add", _ptr(dout), _ptr(inp), n, h, w, c, _ptr(flow),
+                     _ptr(dinp), _ptr(dflow), add, ld, s)
+            else:
+                call("of_warp_bwd_cv", _ptr(dout), _ptr(inp), n, h, w, c, _ptr(flow),
+                     _ptr(dinp), _ptr(dflow), add, ld, ctx.cv, s)
             fa.addend = None
-        else:
+        elif ctx.absolute or ctx.cv == _lib.WARP_REFERENCE:
             call("of_bilinear_bwd" if ctx.absolute else "of_warp_bwd", _ptr(dout), _ptr(inp), n,
                  h, w, c, _ptr(flow), _ptr(dinp), _ptr(dflow), s)
-        return dinp, (dflow if ctx.needs_input_grad[1] else None), None, None
+        else:
+            call("of_warp_bwd_cv", _ptr(dout), _ptr(inp), n, h, w, c, _ptr(flow), _ptr(dinp),
+                 _ptr(dflow), None, 0, ctx.cv, s)
+        return dinp, (dflow if ctx.needs_input_grad[1] else None), None, None, None
 
 
-def warp(inp, flow):
-    return _Warp.apply(inp, flow, False, getattr(flow, "_of_flowadd", None))
+def warp(inp, flow, convention="reference"):
+    """warp_features: ``inp`` sampled at grid + flow.  ``convention`` names the grid
+    (warp_convention above): "reference" (default) or "image"."""
+    return _Warp.apply(inp, flow, False, getattr(flow, "_of_flowadd", None),
+                       warp_convention(convention))
 
 
 def bilinear(inp, points):
@@ -2076,9 +2118,11 @@ class _PhotoLoss(torch.autograd.Function):
     scale directly (the images are constants)."""
 
     @staticmethod
-    def forward(ctx, batch_imgs, fgs, *flows):
+    def forward(ctx, batch_imgs, fgs_wc, *flows):
+        fgs, wc = fgs_wc                 # (FlowGrad per level, warp convention code)
         _check_dev(batch_imgs, *flows)
         ctx.fgs = fgs
+        ctx.wc = wc
         b = batch_imgs.contiguous()
         n, H, W, c = b.shape
         assert c == 6
@@ -2101,9 +2145,9 @@ class _PhotoLoss(torch.autograd.Function):
         nparts = [_lib.lib().of_photo_l1_partials(n, h, w) for h, w in zip(hs, ws_)]
         coefs = [1.0 / (ns * n * h * w * 3) for h, w in zip(hs, ws_)]
         parts = torch.empty(sum(nparts), device=b.device)
-        call("of_photo_l1_fwd_multi", (C.c_void_p * ns)(*[p.data_ptr() for p in pyr]),
-             (C.c_void_p * ns)(*[f.data_ptr() for f in fl]), n, (C.c_int * ns)(*hs),
-             (C.c_int * ns)(*ws_), ns, _ptr(parts), s)
+        _call_cv("of_photo_l1_fwd_multi", wc, (C.c_void_p * ns)(*[p.data_ptr() for p in pyr]),
+                 (C.c_void_p * ns)(*[f.data_ptr() for f in fl]), n, (C.c_int * ns)(*hs),
+                 (C.c_int * ns)(*ws_), ns, _ptr(parts), s)
         offs = [0]
         for k in range(ns):
             offs.append(offs[-1] + nparts[k])
@@ -2141,21 +2185,22 @@ class _PhotoLoss(torch.autograd.Function):
         if lv:
             m = len(lv)
             n = pyr[0].shape[0]
-            call("of_photo_l1_bwd_multi", (C.c_void_p * m)(*[pyr[k].data_ptr() for k, _, _ in lv]),
-                 (C.c_void_p * m)(*[flows[k].data_ptr() for k, _, _ in lv]), n,
-                 (C.c_int * m)(*[pyr[k].shape[1] for k, _, _ in lv]),
-                 (C.c_int * m)(*[pyr[k].shape[2] for k, _, _ in lv]), m,
-                 (C.c_float * m)(*[ctx.coefs[k] for k, _, _ in lv]), _ptr(dloss),
-                 (C.c_void_p * m)(*[o.data_ptr() for _, o, _ in lv]),
-                 (C.c_int * m)(*[ld for _, _, ld in lv]), s)
+            _call_cv("of_photo_l1_bwd_multi", ctx.wc,
+                     (C.c_void_p * m)(*[pyr[k].data_ptr() for k, _, _ in lv]),
+                     (C.c_void_p * m)(*[flows[k].data_ptr() for k, _, _ in lv]), n,
+                     (C.c_int * m)(*[pyr[k].shape[1] for k, _, _ in lv]),
+                     (C.c_int * m)(*[pyr[k].shape[2] for k, _, _ in lv]), m,
+                     (C.c_float * m)(*[ctx.coefs[k] for k, _, _ in lv]), _ptr(dloss),
+                     (C.c_void_p * m)(*[o.data_ptr() for _, o, _ in lv]),
+                     (C.c_int * m)(*[ld for _, _, ld in lv]), s)
         return (None, None, *grads)
 
 
-def photometric_loss(batch_imgs, flows):
+def photometric_loss(batch_imgs, flows, convention="reference"):
     fgs = [getattr(f, "_of_flowgrad", None) for f in flows]
     if any(fg is not None and fg.shape != tuple(f.shape) for fg, f in zip(fgs, flows)):
         fgs = [None] * len(flows)
-    return _PhotoLoss.apply(batch_imgs, fgs, *flows)
+    return _PhotoLoss.apply(batch_imgs, (fgs, warp_convention(convention)), *flows)
 
 
 # ============================================================== flow smoothness =====
@@ -2278,7 +2323,7 @@ class _FlowLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, batch_imgs, fgs, cfg, *flows):
-        weight, edge_alpha, eps = cfg
+        weight, edge_alpha, eps, wc = cfg
         _check_dev(batch_imgs, *flows)
         ctx.fgs = fgs
         b = batch_imgs.contiguous()
@@ -2293,9 +2338,9 @@ class _FlowLoss(torch.autograd.Function):
         nparts = [_lib.lib().of_photo_l1_partials(n, h, w) for h, w in zip(hs, ws_)]
         coefs = [1.0 / (ns * n * h * w * 3) for h, w in zip(hs, ws_)]
         parts = torch.empty(sum(nparts), device=b.device)
-        call("of_photo_l1_fwd_multi", _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
-             _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs),
-             _arr(C.c_int, ws_), ns, _ptr(parts), s)
+        _call_cv("of_photo_l1_fwd_multi", wc, _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
+                 _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs),
+                 _arr(C.c_int, ws_), ns, _ptr(parts), s)
         cv, ch = _smooth_coefs(n, hs, ws_, weight)
         sparts = _smooth_fwd(pyr, fl, edge_alpha, eps, cv, ch)
         offs = [0]
@@ -2310,6 +2355,7 @@ class _FlowLoss(torch.autograd.Function):
              len(groups), _ptr(loss), s)
         ctx.save_for_backward(*pyr, *fl)
         ctx.cfg = (ns, edge_alpha, eps, coefs, cv, ch)
+        ctx.wc = wc
         return loss
 
     @staticmethod
@@ -2338,25 +2384,28 @@ class _FlowLoss(torch.autograd.Function):
             m = len(lv)
             n = pyr[0].shape[0]
             # the photometric gradient writes every output, the smoothness gradient adds
-            call("of_photo_l1_bwd_multi", _arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]),
-                 _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]), n,
-                 _arr(C.c_int, [pyr[k].shape[1] for k, _, _ in lv]),
-                 _arr(C.c_int, [pyr[k].shape[2] for k, _, _ in lv]), m,
-                 _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
-                 _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
-                 _arr(C.c_int, [ld for _, _, ld in lv]), s)
+            _call_cv("of_photo_l1_bwd_multi", ctx.wc,
+                     _arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]),
+                     _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]), n,
+                     _arr(C.c_int, [pyr[k].shape[1] for k, _, _ in lv]),
+                     _arr(C.c_int, [pyr[k].shape[2] for k, _, _ in lv]), m,
+                     _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
+                     _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
+                     _arr(C.c_int, [ld for _, _, ld in lv]), s)
             _smooth_bwd(pyr, flows, lv, edge_alpha, eps, cv, ch, dloss, 1)
         return (None, None, None, *grads)
 
 
-def flow_loss(batch_imgs, flows, smoothness_weight, edge_alpha=0.0, eps=1e-4):
+def flow_loss(batch_imgs, flows, smoothness_weight, edge_alpha=0.0, eps=1e-4,
+              convention="reference"):
     """The training loss with the smoothness regulariser: photometric_loss plus
     ``smoothness_weight`` times flow_smoothness, in one Function (see _FlowLoss)."""
     fgs = [getattr(f, "_of_flowgrad", None) for f in flows]
     if any(fg is not None and fg.shape != tuple(f.shape) for fg, f in zip(fgs, flows)):
         fgs = [None] * len(flows)
     return _FlowLoss.apply(batch_imgs, fgs,
-                           (float(smoothness_weight), float(edge_alpha), float(eps)), *flows)
+                           (float(smoothness_weight), float(edge_alpha), float(eps),
+                            warp_convention(convention)), *flows)
 
 
 # ================================================================== census term =====
@@ -2367,7 +2416,7 @@ def _census_coefs(n, hs, ws, scale):
     return [scale / (ns * n * h * w) for h, w in zip(hs, ws)]
 
 
-def _census_fwd(pyr, fl, radius, coefs, want_grad):
+def _census_fwd(pyr, fl, radius, coefs, want_grad, wc=0):
     """of_census_fwd_multi over every level: (partials, planes).  The partials sum to the
     weighted term (the coefficients are applied in the kernel); planes[l] is the unscaled
     d C_l / d flow that of_census_bwd_multi scales into d(flow), or None without want_grad."""
@@ -2381,13 +2430,13 @@ def _census_fwd(pyr, fl, radius, coefs, want_grad):
     planes = [torch.empty_like(f) for f in fl] if want_grad else None
     wsf = [lib.of_census_workspace_floats(n, h, w) for h, w in zip(hs, ws_)]
     wss = [torch.empty(k, device=fl[0].device) if k > 0 else None for k in wsf]
-    call("of_census_fwd_multi", _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
-         _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs), _arr(C.c_int, ws_),
-         ns, radius, _arr(C.c_float, coefs),
-         _arr(C.c_void_p, [t.data_ptr() if t is not None else None for t in wss])
-         if any(wsf) else None,
-         _arr(C.c_void_p, [p.data_ptr() for p in planes]) if planes is not None else None,
-         _ptr(parts), _stream())
+    _call_cv("of_census_fwd_multi", wc, _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
+             _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs),
+             _arr(C.c_int, ws_), ns, radius, _arr(C.c_float, coefs),
+             _arr(C.c_void_p, [t.data_ptr() if t is not None else None for t in wss])
+             if any(wsf) else None,
+             _arr(C.c_void_p, [p.data_ptr() for p in planes]) if planes is not None else None,
+             _ptr(parts), _stream())
     return parts, planes
 
 
@@ -2410,14 +2459,15 @@ class _Census(torch.autograd.Function):
     loop forms both); the backward scales it.  The images are constants."""
 
     @staticmethod
-    def forward(ctx, batch_imgs, radius, *flows):
+    def forward(ctx, batch_imgs, radius_wc, *flows):
+        radius, wc = radius_wc           # (window radius, warp convention code)
         _check_dev(batch_imgs, *flows)
         assert 1 <= len(flows) <= 8
         fl = [f.contiguous() for f in flows]
         n = fl[0].shape[0]
         pyr = _pyramid6(batch_imgs.contiguous(), fl)
         coefs = _census_coefs(n, [f.shape[1] for f in fl], [f.shape[2] for f in fl], 1.0)
-        parts, planes = _census_fwd(pyr, fl, radius, coefs, any(ctx.needs_input_grad[2:]))
+        parts, planes = _census_fwd(pyr, fl, radius, coefs, any(ctx.needs_input_grad[2:]), wc)
         out = torch.empty((), device=parts.device)
         call("of_sum_partials", _arr(C.c_void_p, [parts.data_ptr()]),
              _arr(C.c_int, [parts.numel()]), _arr(C.c_float, [1.0]), 1, _ptr(out), _stream())
@@ -2448,9 +2498,10 @@ def _census_radius(radius):
     return int(radius)
 
 
-def census_loss(batch_imgs, flows, radius=3):
+def census_loss(batch_imgs, flows, radius=3, convention="reference"):
     """The census term alone (a scalar; plain gradients for the flows)."""
-    return _Census.apply(batch_imgs, _census_radius(radius), *flows)
+    return _Census.apply(batch_imgs, (_census_radius(radius), warp_convention(convention)),
+                         *flows)
 
 
 class _CensusFlowLoss(torch.autograd.Function):
@@ -2461,8 +2512,9 @@ class _CensusFlowLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, batch_imgs, fgs, cfg, *flows):
-        pw, cw, radius, sw, edge_alpha, eps = cfg
+        pw, cw, radius, sw, edge_alpha, eps, wc = cfg
         _check_dev(batch_imgs, *flows)
+        ctx.wc = wc
         assert pw != 0 or cw != 0, "a data term is needed: both data weights are 0"
         ctx.fgs = fgs
         b = batch_imgs.contiguous()
@@ -2483,9 +2535,9 @@ class _CensusFlowLoss(torch.autograd.Function):
         if pw != 0:
             nparts = [_lib.lib().of_photo_l1_partials(n, h, w) for h, w in zip(hs, ws_)]
             parts = torch.empty(sum(nparts), device=b.device)
-            call("of_photo_l1_fwd_multi", _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
-                 _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs),
-                 _arr(C.c_int, ws_), ns, _ptr(parts), s)
+            _call_cv("of_photo_l1_fwd_multi", wc, _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
+                     _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs),
+                     _arr(C.c_int, ws_), ns, _ptr(parts), s)
             off = 0
             for k in range(ns):
                 groups.append((parts.data_ptr() + 4 * off, nparts[k], coefs[k]))
@@ -2495,7 +2547,8 @@ class _CensusFlowLoss(torch.autograd.Function):
         ccoefs = _census_coefs(n, hs, ws_, cw)
         planes = None
         if cw != 0:
-            cparts, planes = _census_fwd(pyr, fl, radius, ccoefs, any(ctx.needs_input_grad[3:]))
+            cparts, planes = _census_fwd(pyr, fl, radius, ccoefs, any(ctx.needs_input_grad[3:]),
+                                         wc)
             groups.append((cparts.data_ptr(), cparts.numel(), 1.0))
             keep.append(cparts)
         cv, ch = _smooth_coefs(n, hs, ws_, sw)
@@ -2538,14 +2591,14 @@ class _CensusFlowLoss(torch.autograd.Function):
             n = pyr[0].shape[0]
             written = 0                # the first term present writes, the others add
             if pw != 0:
-                call("of_photo_l1_bwd_multi",
-                     _arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]),
-                     _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]), n,
-                     _arr(C.c_int, [pyr[k].shape[1] for k, _, _ in lv]),
-                     _arr(C.c_int, [pyr[k].shape[2] for k, _, _ in lv]), m,
-                     _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
-                     _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
-                     _arr(C.c_int, [ld for _, _, ld in lv]), s)
+                _call_cv("of_photo_l1_bwd_multi", ctx.wc,
+                         _arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]),
+                         _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]), n,
+                         _arr(C.c_int, [pyr[k].shape[1] for k, _, _ in lv]),
+                         _arr(C.c_int, [pyr[k].shape[2] for k, _, _ in lv]), m,
+                         _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
+                         _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
+                         _arr(C.c_int, [ld for _, _, ld in lv]), s)
                 written = 1
             if cw != 0:
                 _census_bwd(planes, lv, ccoefs, dloss, written)
@@ -2556,7 +2609,7 @@ class _CensusFlowLoss(torch.autograd.Function):
 
 
 def census_flow_loss(batch_imgs, flows, census_weight, census_radius=3, photometric_weight=1.0,
-                     smoothness_weight=0.0, edge_alpha=0.0, eps=1e-4):
+                     smoothness_weight=0.0, edge_alpha=0.0, eps=1e-4, convention="reference"):
     """The training loss with the census data term: ``photometric_weight`` times
     photometric_loss plus ``census_weight`` times census_loss plus ``smoothness_weight`` times
     flow_smoothness, in one Function (see _CensusFlowLoss).  At least one data weight must be
@@ -2565,5 +2618,5 @@ def census_flow_loss(batch_imgs, flows, census_weight, census_radius=3, photomet
     if any(fg is not None and fg.shape != tuple(f.shape) for fg, f in zip(fgs, flows)):
         fgs = [None] * len(flows)
     cfg = (float(photometric_weight), float(census_weight), _census_radius(census_radius),
-           float(smoothness_weight), float(edge_alpha), float(eps))
+           float(smoothness_weight), float(edge_alpha), float(eps), warp_convention(convention))
     return _CensusFlowLoss.apply(batch_imgs, fgs, cfg, *flows)

@@ -169,6 +169,18 @@ class KerasAdam:
             s.bn_guard.after_update(self._lr)
 
 
+def check_warp_conventions(flow_net, loss_layer):
+    """The net's warp and the loss layer's must sample one convention: training across two is
+    never meant (the loss would score flows the net's warps read differently).  An object
+    without the attribute (TwoLayerHead, a custom loss) counts as "reference"."""
+    net_cv = getattr(flow_net, "warp_convention", "reference")
+    loss_cv = getattr(loss_layer, "warp_convention", "reference")
+    if net_cv != loss_cv:
+        raise ValueError("the net warps in the %r convention and the loss layer in %r: "
+                         "build both with the same warp_convention" % (net_cv, loss_cv))
+    return net_cv
+
+
 class Trainer:
     """Holds the model, optimizer, loss and (optional) DP reducer; ``train_step`` is the
     hot loop body of train.py:72-82."""
@@ -181,7 +193,9 @@ class Trainer:
         communicator over all ranks of the default group), "torch" otherwise."""
         self.flow_net = flow_net
         self.optimizer = optimizer or KerasAdam(flow_net.store)
-        self.loss_layer = loss_layer or LossLayer()
+        self.loss_layer = loss_layer or LossLayer(
+            warp_convention=getattr(flow_net, "warp_convention", "reference"))
+        check_warp_conventions(flow_net, self.loss_layer)
         if data_parallel is None:
             data_parallel = comm is not None or (torch.distributed.is_initialized() and
                                                  torch.distributed.get_world_size() > 1)
@@ -383,6 +397,9 @@ def build_parser():
                     help="drop an update whose gradient norm is inf or NaN")
     ap.add_argument("--log-grad-norm", action="store_true",
                     help="record the global gradient norm of every step in the step log")
+    ap.add_argument("--warp-convention", default="reference", choices=("reference", "image"),
+                    help="the grid every warp adds the flow to: the reference's transposed grid "
+                         "(default) or image coordinates (flow = (x, y) displacement)")
     g = ap.add_argument_group(
         "augmentation (with --kitti only)", "seeded by --seed; both images of a pair get the "
         "same draw; an --aug-* flag without --augment starts from no augmentation")
@@ -407,6 +424,32 @@ def build_parser():
     return ap
 
 
+def header_record(args, augment=None):
+    """The step log's header record (no "step" key) for a run with any non-default loss,
+    augmentation, clipping or warp-convention option; None for a default run, whose log holds
+    step records only."""
+    census = (args.census_weight != 0.0 or args.census_radius != 3 or
+              args.photometric_weight != 1.0)
+    clip = args.clip_norm is not None or args.skip_nonfinite or args.log_grad_norm
+    image = args.warp_convention == "image"
+    if not (args.smoothness_weight or args.edge_alpha or augment is not None or census or clip
+            or image):
+        return None
+    head = {"header": True, "smoothness_weight": args.smoothness_weight,
+            "edge_alpha": args.edge_alpha}
+    if census:
+        head.update(census_weight=args.census_weight, census_radius=args.census_radius,
+                    photometric_weight=args.photometric_weight)
+    if augment is not None:
+        head["augment"] = augment.as_dict()
+    if clip:
+        head.update(clip_norm=args.clip_norm, skip_nonfinite=args.skip_nonfinite,
+                    log_grad_norm=args.log_grad_norm)
+    if image:
+        head["warp_convention"] = args.warp_convention
+    return head
+
+
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -422,7 +465,8 @@ def main(argv=None):
         loss_layer = LossLayer(args.smoothness_weight, args.edge_alpha,
                                census_weight=args.census_weight,
                                census_radius=args.census_radius,
-                               photometric_weight=args.photometric_weight)
+                               photometric_weight=args.photometric_weight,
+                               warp_convention=args.warp_convention)
     except ValueError as e:
         ap.error(str(e))
     try:
@@ -433,28 +477,16 @@ def main(argv=None):
 
     rank, world, local = init_from_env()
     torch.cuda.set_device(local)
-    net = build_flow_net(args.height, args.width, args.pretrained, seed=args.seed)
+    net = build_flow_net(args.height, args.width, args.pretrained, seed=args.seed,
+                         warp_convention=args.warp_convention)
     if rank == 0:
         net.summary()
     opt = KerasAdam(net.store, learning_rate=args.lr, global_clipnorm=args.clip_norm,
                     skip_nonfinite=args.skip_nonfinite, track_grad_norm=args.log_grad_norm)
     trainer = Trainer(net, opt, loss_layer)
     log = open(args.log, "a") if (args.log and rank == 0) else None
-    census = (args.census_weight != 0.0 or args.census_radius != 3 or
-              args.photometric_weight != 1.0)
-    if log and (args.smoothness_weight or args.edge_alpha or augment is not None or census
-                or clip):
-        # header record (no "step" key); a default run's log holds step records only, as before
-        head = {"header": True, "smoothness_weight": args.smoothness_weight,
-                "edge_alpha": args.edge_alpha}
-        if census:
-            head.update(census_weight=args.census_weight, census_radius=args.census_radius,
-                        photometric_weight=args.photometric_weight)
-        if augment is not None:
-            head["augment"] = augment.as_dict()
-        if clip:
-            head.update(clip_norm=args.clip_norm, skip_nonfinite=args.skip_nonfinite,
-                        log_grad_norm=args.log_grad_norm)
+    head = header_record(args, augment)
+    if log and head is not None:
         log.write(json.dumps(head) + "\n")
     reader = None
     if args.kitti:
