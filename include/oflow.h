@@ -753,6 +753,68 @@ int of_reader_next_aug(of_reader* r, void* dev_raw, int64_t cap, const of_augmen
                        of_augment* dev_params, float* out, int out_h, int out_w,
                        int32_t* pair_index, int32_t* swapped, void* stream);
 
+/* ==== Evaluation against KITTI flow ground truth (build-added; the reference has none,
+ * SURVEY.md F7) ============================================================================ */
+
+/* KITTI 2015 flow maps (flow_occ / flow_noc) are 16-bit RGB PNGs.  of_png_read_u16 decodes a
+ * colour-type-2, depth-16 PNG into h x w x 3 host-order uint16 in R, G, B order, the samples
+ * not reduced (cap: uint16 elements `out` holds); any other colour type or depth is OF_EINVAL
+ * with a message naming what the file holds.  of_png_write_u16 writes that format from
+ * h x w x 3 R, G, B samples; flags as of_png_write. */
+int of_png_read_u16(const char* path, uint16_t* out, int64_t cap, int* h, int* w);
+int of_png_write_u16(const char* path, const uint16_t* rgb, int h, int w, int flags);
+
+/* One image's sums, what of_flow_eval writes per image. */
+typedef struct of_flow_eval_result {
+  double sum_epe;      /* sum of the end-point error over the valid pixels */
+  int64_t n_valid;     /* pixels with B != 0 */
+  int64_t n_outlier;   /* valid pixels with epe > 3 and epe > 5 % of |ground truth| */
+} of_flow_eval_result;
+
+/* End-point error and outlier count of n flows against KITTI ground truth, in one pass over
+ * the ground-truth pixels: the flow is upsampled, scaled, compared and reduced per pixel and
+ * never written at full resolution.
+ *   flow: (n, fh, fw, 2) fp32 in the image convention (OF_WARP_IMAGE), in pixels of its own grid.
+ *   dev_gt_raw (device memory): of_image_desc[n] padded to 256 bytes, then n maps of
+ *   h_i x w_i x 3 uint16 (R, G, B as of_png_read_u16 gives them), map i dense at byte
+ *   desc[i].offset.  Sizes are per image.  A map at a 16-byte aligned offset is read with
+ *   16-byte loads (eight pixels = three loads), any other offset byte by byte.
+ * Per ground-truth pixel (x, y) of image i (gh = h_i, gw = w_i):
+ *   sx = (x + 0.5) * fw / gw - 0.5 clamped to [0, fw-1], sy likewise (half-pixel centres,
+ *   border replication, as of_augment_pairs);  x0 = floor(sx), x1 = min(x0+1, fw-1),
+ *   fx = sx - x0 (same for y).  x0 and fx come from the exact integers sx = ((2x+1) fw - gw) /
+ *   (2 gw) (x0 the integer quotient, fx = (float)remainder / (float)(2 gw), one rounding): sx
+ *   formed in fp32 is off by half an ulp of its size, 1.5e-5 at 1242 columns, which a flow
+ *   that changes by 80 px between neighbouring cells turns into 1.2e-3 px.  Then in fp32:
+ *   per channel top = p00 + (p01-p00)*fx, bot = p10 + (p11-p10)*fx,
+ *   val = top + (bot-top)*fy;  u = val0 * (gw / fw), v = val1 * (gh / fh)   (native pixels);
+ *   gu = ((float)R - 32768) / 64, gv = ((float)G - 32768) / 64, valid iff B != 0 (the KITTI
+ *   devkit's decode);  epe = sqrtf((u-gu)^2 + (v-gv)^2);
+ *   outlier iff valid and epe > 3 and epe > 0.05f * sqrtf(gu^2 + gv^2)   (the devkit's 3 px /
+ *   5 % rule without its division: a zero ground-truth vector with epe > 3 is an outlier).
+ * out: n x of_flow_eval_result.  Deterministic: each workgroup sums its pixels in a fixed order
+ * (epe summed in double), wave shuffle tree, LDS, one record into `partials`; a second launch
+ * sums an image's records in index order.  No atomics; two calls on equal input give equal
+ * bits.  partials: npartials = of_flow_eval_partials(n, max_gh, max_gw) records of 24 bytes,
+ * 8-byte aligned, where max_gh / max_gw bound every map of the batch (a larger map is still
+ * summed whole, by fewer workgroups than it would get).
+ * host_descs (optional): the caller's host copy of the n descriptors, checked before anything
+ * is launched (h, w >= 1, h * w < 2^31, offset >= 0, and, when gt_bytes > 0, the map inside
+ * gt_bytes); with NULL nothing is checked and a map with h <= 0 or w <= 0 counts no pixel.
+ * OF_EINVAL (and no launch) for a NULL flow / dev_gt_raw / partials / out, n < 0 or > 65535,
+ * fh or fw < 1, npartials that of_flow_eval_partials cannot have returned for this n, a bad
+ * host descriptor, flow / partials / out not 8-byte or dev_gt_raw not 16-byte aligned.
+ * n == 0 launches nothing. */
+int of_flow_eval_partials(int n, int max_gh, int max_gw);
+int of_flow_eval(const float* flow, int n, int fh, int fw, const void* dev_gt_raw,
+                 const of_image_desc* host_descs, int64_t gt_bytes, double* partials,
+                 int npartials, void* out, void* stream);
+/* The same sampled and scaled (u, v) (one __device__ function serves both) of every pixel of a
+ * gh x gw image: out (n, gh, gw, 2) fp32.  For predictions and KITTI-format result files.
+ * OF_EINVAL (and no launch) for a NULL pointer, n < 0, fh, fw, gh or gw < 1. */
+int of_flow_upsample(const float* flow, int n, int fh, int fw, int gh, int gw, float* out,
+                     void* stream);
+
 /* ==== SURVEY.md §8 f row 2: TensorFlow checkpoint bundles (save_weights / load_weights) ===== */
 
 /* CRC32C (Castagnoli) of n bytes, continuing from crc (0 to start; unmasked).  The bundle's

@@ -156,6 +156,12 @@ PROTOTYPES = {
     "of_augment_pairs": (I, [P, I, I, I, P, P, P]),
     "of_reader_next_aug": (I, [P, P, I64, P, P, P, I, I, C.POINTER(C.c_int32),
                                C.POINTER(C.c_int32), P]),
+    # evaluation against KITTI flow ground truth (evaluate.py)
+    "of_png_read_u16": (I, [C.c_char_p, P, I64, C.POINTER(I), C.POINTER(I)]),
+    "of_png_write_u16": (I, [C.c_char_p, P, I, I, I]),
+    "of_flow_eval_partials": (I, [I, I, I]),
+    "of_flow_eval": (I, [P, I, I, I, P, P, I64, P, I, P, P]),
+    "of_flow_upsample": (I, [P, I, I, I, I, I, P, P]),
     "of_flow_color": (I, [P, I, I, I, P, P, P]),
     "of_flow_intensity": (I, [P, I64, P, P]),
     "of_crc32c": (C.c_uint32, [P, I64, C.c_uint32]),   # checkpoint bundles (row 2)

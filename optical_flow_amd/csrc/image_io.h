@@ -1,5 +1,6 @@
 // Host image I/O shared by the data path (SURVEY.md §8 f row 1: data_reader.py) and the flow
-// visualisation (row 4: drawing.py).  PNG only: KITTI raw frames are 8-bit RGB PNGs.
+// visualisation (row 4: drawing.py).  PNG only: KITTI raw frames are 8-bit RGB PNGs, KITTI flow
+// maps 16-bit RGB PNGs.
 #pragma once
 #include <stdint.h>
 
@@ -32,6 +33,15 @@ bool decode_bgr(const uint8_t* data, size_t n, uint8_t* out, size_t cap, Info& i
 // heuristic, 6 = cycle 0..4 by row (decoder coverage).  level: zlib level 0-9.
 bool encode(const uint8_t* img, int h, int w, int c, int filter, int level,
             std::vector<uint8_t>& out, std::string& err);
+
+// Decode a colour-type-2, depth-16 PNG (KITTI flow ground truth) to h x w x 3 host-order
+// uint16, R, G, B, samples not reduced; any other colour type or depth is an error that names
+// what was found.  `out` holds at least `cap` >= h*w*3 elements.
+bool decode_rgb16(const uint8_t* data, size_t n, uint16_t* out, size_t cap, Info& info,
+                  std::string& err);
+// Encode h x w x 3 uint16 R, G, B as a 16-bit RGB PNG; filter and level as encode().
+bool encode_rgb16(const uint16_t* rgb, int h, int w, int filter, int level,
+                  std::vector<uint8_t>& out, std::string& err);
 
 }  // namespace png
 }  // namespace oflow

@@ -4,7 +4,8 @@
 // stream, zlib stream of filtered scanlines (Adam7 passes when interlaced), filter types
 // 0-4, then the conversion cv2.imread(path) applies with IMREAD_COLOR: 8-bit BGR, gray
 // replicated, palette expanded, alpha dropped, 16-bit samples reduced to their high byte,
-// 1/2/4-bit gray scaled to 0..255.
+// 1/2/4-bit gray scaled to 0..255.  KITTI's flow maps are 16-bit RGB and must not be reduced:
+// decode_rgb16 / encode_rgb16 share everything with the 8-bit path but that last conversion.
 #include <zlib.h>
 
 #include <algorithm>
@@ -153,12 +154,14 @@ static bool put_pixel(const uint8_t* row, int x, const Info& in, const uint8_t* 
   return true;
 }
 
-bool decode_bgr(const uint8_t* d, size_t n, uint8_t* out, size_t cap, Info& in, std::string& err) {
-  if (!parse_info(d, n, in, err)) return false;
-  if (cap < (size_t)in.w * in.h * 3) { err = "PNG: output buffer too small"; return false; }
+// Everything of a decode but the last conversion step, for a header parse_info accepted: the
+// chunk walk (PLTE into plte / nplte, IDAT concatenated), the inflate, then per scanline of
+// every pass the unfilter and emit(row, x, ox, oy) for pixel x of the unfiltered row, which
+// belongs at column ox, row oy of the image.
+template <class Emit>
+static bool decode_walk(const uint8_t* d, size_t n, const Info& in, uint8_t* plte, int& nplte,
+                        std::string& err, Emit emit) {
   // ---- chunk walk: PLTE + concatenated IDAT ----
-  uint8_t plte[256 * 3];
-  int nplte = 0;
   std::vector<uint8_t> idat;
   size_t pos = 8;
   bool end = false;
@@ -228,14 +231,42 @@ bool decode_bgr(const uint8_t* d, size_t n, uint8_t* out, size_t cap, Info& in, 
       const int oy = in.interlace ? ay0[p] + y * ady[p] : y;
       for (int x = 0; x < pw[p]; ++x) {
         const int ox = in.interlace ? ax0[p] + x * adx[p] : x;
-        if (!put_pixel(row, x, in, plte, nplte, out + ((size_t)oy * in.w + ox) * 3, err))
-          return false;
+        if (!emit(row, x, ox, oy)) return false;
       }
       prev = row;
       p_row += 1 + rb;
     }
   }
   return true;
+}
+
+bool decode_bgr(const uint8_t* d, size_t n, uint8_t* out, size_t cap, Info& in, std::string& err) {
+  if (!parse_info(d, n, in, err)) return false;
+  if (cap < (size_t)in.w * in.h * 3) { err = "PNG: output buffer too small"; return false; }
+  uint8_t plte[256 * 3];
+  int nplte = 0;
+  return decode_walk(d, n, in, plte, nplte, err, [&](const uint8_t* row, int x, int ox, int oy) {
+    return put_pixel(row, x, in, plte, nplte, out + ((size_t)oy * in.w + ox) * 3, err);
+  });
+}
+
+bool decode_rgb16(const uint8_t* d, size_t n, uint16_t* out, size_t cap, Info& in,
+                  std::string& err) {
+  if (!parse_info(d, n, in, err)) return false;
+  if (in.ctype != 2 || in.depth != 16) {
+    err = "PNG: not a 16-bit RGB image (colour type " + std::to_string(in.ctype) +
+          ", bit depth " + std::to_string(in.depth) + ")";
+    return false;
+  }
+  if (cap < (size_t)in.w * in.h * 3) { err = "PNG: output buffer too small"; return false; }
+  uint8_t plte[256 * 3];
+  int nplte = 0;
+  return decode_walk(d, n, in, plte, nplte, err, [&](const uint8_t* row, int x, int ox, int oy) {
+    const uint8_t* s = row + (size_t)x * 6;          // big-endian R, G, B
+    uint16_t* o = out + ((size_t)oy * in.w + ox) * 3;
+    for (int k = 0; k < 3; ++k) o[k] = (uint16_t)(s[2 * k] << 8 | s[2 * k + 1]);
+    return true;
+  });
 }
 
 static void chunk(std::vector<uint8_t>& out, const char* type, const uint8_t* body, size_t len) {
@@ -246,22 +277,16 @@ static void chunk(std::vector<uint8_t>& out, const char* type, const uint8_t* bo
   put32(out, (uint32_t)crc32(0, out.data() + at, (uInt)(len + 4)));
 }
 
-bool encode(const uint8_t* img, int h, int w, int c, int filter, int level,
-            std::vector<uint8_t>& out, std::string& err) {
-  if (h <= 0 || w <= 0 || !(c == 1 || c == 3 || c == 4) || filter < 0 || filter > 6 ||
-      level < 0 || level > 9) {
-    err = "png encode: bad arguments";
-    return false;
-  }
-  const size_t rb = (size_t)w * c;
+// Filter, deflate and wrap h scanlines of rb bytes, bpp bytes per pixel, as a PNG of the given
+// bit depth and colour type; fill(y, row) writes scanline y in PNG sample order.
+template <class Fill>
+static bool encode_rows(int h, int w, size_t rb, int bpp, int depth, int ctype, int filter,
+                        int level, Fill fill, std::vector<uint8_t>& out, std::string& err) {
+  const int c = bpp;
   std::vector<uint8_t> raw((size_t)h * (rb + 1));
   std::vector<uint8_t> cur(rb), prev(rb, 0), cand(rb);
   for (int y = 0; y < h; ++y) {
-    const uint8_t* src = img + (size_t)y * rb;
-    for (int x = 0; x < w; ++x) {   // BGR(A) -> RGB(A)
-      for (int k = 0; k < c; ++k) cur[(size_t)x * c + k] = src[(size_t)x * c + k];
-      if (c >= 3) std::swap(cur[(size_t)x * c], cur[(size_t)x * c + 2]);
-    }
+    fill(y, cur.data());
     auto apply = [&](int t, uint8_t* dst) {
       for (size_t i = 0; i < rb; ++i) {
         const int a = i >= (size_t)c ? cur[i - c] : 0, b = y ? prev[i] : 0;
@@ -298,13 +323,51 @@ bool encode(const uint8_t* img, int h, int w, int c, int filter, int level,
   const uint8_t wh[8] = {(uint8_t)(W >> 24), (uint8_t)(W >> 16), (uint8_t)(W >> 8), (uint8_t)W,
                          (uint8_t)(H >> 24), (uint8_t)(H >> 16), (uint8_t)(H >> 8), (uint8_t)H};
   memcpy(ihdr, wh, 8);
-  ihdr[8] = 8;
-  ihdr[9] = c == 1 ? 0 : c == 3 ? 2 : 6;
+  ihdr[8] = (uint8_t)depth;
+  ihdr[9] = (uint8_t)ctype;
   ihdr[10] = ihdr[11] = ihdr[12] = 0;
   chunk(out, "IHDR", ihdr, 13);
   chunk(out, "IDAT", z.data(), zlen);
   chunk(out, "IEND", nullptr, 0);
   return true;
+}
+
+bool encode(const uint8_t* img, int h, int w, int c, int filter, int level,
+            std::vector<uint8_t>& out, std::string& err) {
+  if (h <= 0 || w <= 0 || !(c == 1 || c == 3 || c == 4) || filter < 0 || filter > 6 ||
+      level < 0 || level > 9) {
+    err = "png encode: bad arguments";
+    return false;
+  }
+  const size_t rb = (size_t)w * c;
+  return encode_rows(h, w, rb, c, 8, c == 1 ? 0 : c == 3 ? 2 : 6, filter, level,
+                     [&](int y, uint8_t* cur) {
+                       const uint8_t* src = img + (size_t)y * rb;
+                       for (int x = 0; x < w; ++x) {   // BGR(A) -> RGB(A)
+                         for (int k = 0; k < c; ++k) cur[(size_t)x * c + k] = src[(size_t)x * c + k];
+                         if (c >= 3) std::swap(cur[(size_t)x * c], cur[(size_t)x * c + 2]);
+                       }
+                     },
+                     out, err);
+}
+
+bool encode_rgb16(const uint16_t* rgb, int h, int w, int filter, int level,
+                  std::vector<uint8_t>& out, std::string& err) {
+  if (h <= 0 || w <= 0 || w > (1 << 15) || h > (1 << 15) || filter < 0 || filter > 6 ||
+      level < 0 || level > 9) {
+    err = "png encode: bad arguments";
+    return false;
+  }
+  const size_t rb = (size_t)w * 6;
+  return encode_rows(h, w, rb, 6, 16, 2, filter, level,
+                     [&](int y, uint8_t* cur) {
+                       const uint16_t* src = rgb + (size_t)y * w * 3;
+                       for (size_t k = 0; k < (size_t)w * 3; ++k) {   // big-endian samples
+                         cur[2 * k] = (uint8_t)(src[k] >> 8);
+                         cur[2 * k + 1] = (uint8_t)src[k];
+                       }
+                     },
+                     out, err);
 }
 
 }  // namespace png
@@ -351,6 +414,35 @@ int of_png_write(const char* path, const uint8_t* img, int h, int w, int c, int 
   const size_t put = fwrite(out.data(), 1, out.size(), f);
   const int cl = fclose(f);
   if (put != out.size() || cl != 0) return fail(OF_EINVAL, std::string("png_write: short write ") + path);
+  return OF_OK;
+}
+
+int of_png_read_u16(const char* path, uint16_t* out, int64_t cap, int* h, int* w) {
+  OF_CHECK_ARG(path && out && h && w && cap >= 0, "png_read_u16: null argument");
+  std::vector<uint8_t> file;
+  std::string err;
+  png::Info in;
+  if (!png::read_file(path, file, err)) return fail(OF_EINVAL, err);
+  if (!png::decode_rgb16(file.data(), file.size(), out, (size_t)cap, in, err))
+    return fail(OF_EINVAL, err + ": " + path);
+  *h = in.h;
+  *w = in.w;
+  return OF_OK;
+}
+
+int of_png_write_u16(const char* path, const uint16_t* rgb, int h, int w, int flags) {
+  OF_CHECK_ARG(path && rgb, "png_write_u16: null argument");
+  const int filter = flags & 0xff, lbits = (flags >> 8) & 0xf;     // as of_png_write
+  std::vector<uint8_t> out;
+  std::string err;
+  if (!png::encode_rgb16(rgb, h, w, filter, lbits ? lbits - 1 : 6, out, err))
+    return fail(OF_EINVAL, err);
+  FILE* f = fopen(path, "wb");
+  if (!f) return fail(OF_EINVAL, std::string("png_write_u16: cannot create ") + path);
+  const size_t put = fwrite(out.data(), 1, out.size(), f);
+  const int cl = fclose(f);
+  if (put != out.size() || cl != 0)
+    return fail(OF_EINVAL, std::string("png_write_u16: short write ") + path);
   return OF_OK;
 }
 

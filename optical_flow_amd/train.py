@@ -400,6 +400,11 @@ def build_parser():
     ap.add_argument("--warp-convention", default="reference", choices=("reference", "image"),
                     help="the grid every warp adds the flow to: the reference's transposed grid "
                          "(default) or image coordinates (flow = (x, y) displacement)")
+    ap.add_argument("--eval-kitti-flow", default=None, metavar="ROOT",
+                    help="KITTI 2015 flow root: EPE and Fl-all against its ground truth after "
+                         "every --eval-every epochs and at the end (needs --warp-convention image)")
+    ap.add_argument("--eval-every", type=int, default=1, metavar="N",
+                    help="epochs between evaluations (with --eval-kitti-flow)")
     g = ap.add_argument_group(
         "augmentation (with --kitti only)", "seeded by --seed; both images of a pair get the "
         "same draw; an --aug-* flag without --augment starts from no augmentation")
@@ -422,6 +427,19 @@ def build_parser():
     g.add_argument("--aug-color-gain", type=float, default=None, metavar="A",
                    help="per-channel gain uniform in [1-A, 1+A]")
     return ap
+
+
+def check_eval_args(args):
+    """--eval-kitti-flow measures image displacements, so it needs --warp-convention image;
+    --eval-every counts epochs.  ValueError otherwise (main turns it into a parser error)."""
+    if args.eval_kitti_flow is None:
+        return
+    if args.warp_convention != "image":
+        raise ValueError("--eval-kitti-flow needs --warp-convention image: a reference-convention "
+                         "flow is not an image displacement, its error against ground truth "
+                         "means nothing")
+    if args.eval_every < 1:
+        raise ValueError("--eval-every must be >= 1, got %d" % args.eval_every)
 
 
 def header_record(args, augment=None):
@@ -447,6 +465,8 @@ def header_record(args, augment=None):
                     log_grad_norm=args.log_grad_norm)
     if image:
         head["warp_convention"] = args.warp_convention
+    if args.eval_kitti_flow is not None:
+        head.update(eval_kitti_flow=args.eval_kitti_flow, eval_every=args.eval_every)
     return head
 
 
@@ -460,6 +480,11 @@ def main(argv=None):
     if augment is not None and not args.kitti:
         ap.error("--augment / --aug-* apply only with --kitti: without it the driver trains on "
                  "synthetic pairs, which are not augmented")
+
+    try:
+        check_eval_args(args)
+    except ValueError as e:
+        ap.error(str(e))
 
     try:
         loss_layer = LossLayer(args.smoothness_weight, args.edge_alpha,
@@ -494,6 +519,10 @@ def main(argv=None):
         reader = AsyncReader(ReaderOpts(args.kitti, args.batch, args.height, args.width,
                                         args.nworkers, seed=args.seed + rank, augment=augment))
     nbatches = reader.nbatches if reader is not None else args.steps
+    eval_frames = None
+    if args.eval_kitti_flow is not None and rank == 0:
+        from .evaluate import evaluate, list_kitti_flow
+        eval_frames = list_kitti_flow(args.eval_kitti_flow)      # a bad root fails before training
     step = 0
     for epoch in range(args.epochs):
         if epoch == args.lr_drop_epoch:
@@ -526,6 +555,14 @@ def main(argv=None):
             print("\nEpoch computed in %.3fs" % (time.time() - t0))
             if args.save_dir:
                 net.save_weights(os.path.join(args.save_dir, "flow_net_%d" % epoch, "weights"))
+            if eval_frames is not None and ((epoch + 1) % args.eval_every == 0 or
+                                            epoch == args.epochs - 1):
+                res = evaluate(net, eval_frames, nworkers=args.nworkers)
+                res.pop("per_image")
+                line = json.dumps({"eval": res, "epoch": epoch})
+                print(line, flush=True)
+                if log:
+                    log.write(line + "\n")
     if log:
         log.close()
     if reader is not None:
