@@ -607,10 +607,11 @@ int of_timing_enable(int on);
  * key 38 = extra dynamic LDS bytes per own_window workgroup (an occupancy probe; default 0);
  * key 39 = timing ablation: the split 3x3 input gradients without their act' source reads
  * (RESULTS ARE WRONG; default 0);
- * key 40 = the x halo of the 9-tap weight gradients (conv_wgrad_tile_x3b, conv_wgrad_tile_b16):
- * one pixel-major image per tile, every value loaded and split once, read with transposing LDS
- * reads and double-buffered (1, default), or three pixel-shifted copies, single-buffered (0:
- * the conv_wgrad_tile_x3b_c3 / _b16_c3 kernels; bitwise the same gradients). */
+ * key 40 = the x halo of the 3-tap and 9-tap weight gradients (conv_wgrad_tile_x3,
+ * conv_wgrad_tile_x3b, conv_wgrad_tile_b16): one pixel-major image per tile, every value loaded
+ * and split once, read with transposing LDS reads and double-buffered (1, default), or three
+ * pixel-shifted copies, single-buffered (0: the conv_wgrad_tile_x3_c3 / _x3b_c3 / _b16_c3
+ * kernels; bitwise the same gradients). */
 int of_set_tuning(int key, int value);
 int of_timing_read(int max, int* kinds, double* flops, float* ms);
 

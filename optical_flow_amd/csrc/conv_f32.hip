@@ -2879,12 +2879,22 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_tile_bf16(GemmArgs a) {
 // 32 co x the 3 taps of one kernel row: 48 accumulator registers, so three waves fit per
 // SIMD) and walks XH x 16 output-pixel tiles of its K slice (XH = 8; 4 for the 64-channel
 // input blocks, whose halo is twice as wide).  The x halo ((XH + 2) rows x 18 px) is staged once
-// per tile as three split planes x three copies shifted by
-// s = 0, 1, 2 pixels (aligned 16-byte A fragments, the swizzles of conv_wgrad_tile_bf16);
-// it is single-buffered (92 / 110 KB) and register-staged one tile ahead.  dy never enters LDS:
+// per tile, every value loaded and split once (one slot = 4 channels of a pixel), into the
+// 9-tap form's pixel-major image [plane][halo row][halo px][CIB channels] bf16 with its swizzle
+// (wgx3b_sw).  The A fragment of v_mfma_f32_32x32x16_bf16 (8 consecutive pixels of one channel
+// per lane) is two transposing reads per plane: the 16-lane group g = lane >> 4 takes channels
+// 16 (g & 1) .. + 15 x pixels 8 (g >> 1) + s + 4 h .. + 3 (h = 0, 1), so the two groups of a
+// 32-lane half read the two 32-byte blocks of 4 consecutive pixels: 256 bytes on 64 distinct
+// banks for both CIB, and the 8-byte staging stores of a half cover 256 contiguous bytes.  Two
+// images (69 / 83 KB): tile t + 1's float4s are loaded at the top of tile t and split into the
+// other image between its k-steps, one barrier per tile.  dy never enters LDS:
 // a lane loads its B fragment (8 pixels of one channel, coalesced across the 32 channels of
 // a pixel) straight from L2 one k-step ahead and splits it in registers (the three kernel-row
 // waves of a channel block read the same dy lines).  Output: the split-K slabs of the other wgrad kernels.
+// STG = 0 (conv_wgrad_tile_x3_c3, of_set_tuning key 40 = 0) is the earlier staging, kept for
+// A/B and as the bitwise reference: three split planes x three copies shifted by s = 0, 1, 2
+// pixels (aligned 16-byte A fragments, the swizzles of conv_wgrad_tile_bf16), each loaded and
+// split on its own, single-buffered (92 / 110 KB), stored between two barriers.
 // conv_wgrad_tile_x3 pixel tiles: XH rows x 16 px (8 rows where the halo fits LDS)
 int wgx3_rows(int cfg) { return cfg == 2 || cfg == 3 ? 4 : 8; }
 
@@ -3215,14 +3225,34 @@ __global__ __launch_bounds__(256) void stem_bn_final(const float* __restrict__ s
   if (dbias) dbias[co] = accum ? dbias[co] + db : db;
 }
 
-template <int WAVES_CI, int WAVES_CO, int WAVES_R, int XH>
-__global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1) void conv_wgrad_tile_x3(GemmArgs a) {
+// Swizzle of the pixel-major halo image's 32-byte channel blocks by the halo column hx (the
+// 3-tap and 9-tap weight gradients).  9-tap fragments: bit 3 of hx moves the two 16-lane groups
+// of a half (pixels 8 apart) to different blocks; on 128-byte pixel rows (CIB = 64) bit 1 of hx
+// moves the rows 2 apart of one group (256 bytes) as well.  3-tap fragments (a half = the two
+// blocks of a 64-byte pair x 4 consecutive pixels): bit 0 stays inside the pair, and on 128-byte
+// rows bit 1 puts the pairs of pixels 2 apart on the two halves of the banks.
+template <int CIB>
+__device__ __forceinline__ int wgx3b_sw(int hx) {
+  return ((hx >> 3) & 1) | (CIB == 64 ? ((hx >> 1) & 1) << 1 : 0);
+}
+
+template <int WAVES_CI, int WAVES_CO, int WAVES_R, int XH, int STG>
+__device__ __forceinline__ void wgrad_x3_body(const GemmArgs& a) {
   constexpr int NT = 64 * WAVES_CI * WAVES_CO * WAVES_R;
   static_assert(WAVES_R == 3, "one kernel row per wave group");
+  static_assert(STG == 0 || STG == 1, "staging: three shifted copies / one pixel-major image");
   constexpr int CIB = 32 * WAVES_CI, COB = 32 * WAVES_CO, KS = 3, HH = XH + KS - 1, NP = 3;
-  constexpr int XQ = HH * KS * 2 * (CIB / 4), XS = (XQ + NT - 1) / NT;   // (hy, s, half, ci quad)
-  constexpr int PL = KS * HH * CIB * 2;                              // uint4 per plane
-  __shared__ uint4 Xs[NP * PL];
+  static_assert(CIB == 32 || CIB == 64, "wgx3b_sw");
+  // STG 0: slots (hy, s, half, ci quad) of 8 pixels; STG 1: slots (hy, hx, ci quad) of 1 pixel
+  constexpr int HW = TT_W + KS - 1;
+  constexpr int XQ = STG ? HH * HW * (CIB / 4) : HH * KS * 2 * (CIB / 4), XS = (XQ + NT - 1) / NT;
+  static_assert(NT % (CIB / 4) == 0, "a thread keeps its channel quad in every slot");
+  constexpr int PL = KS * HH * CIB * 2;                              // STG 0: uint4 per plane
+  constexpr int PXB = CIB * 2;                     // STG 1: bytes per halo pixel and plane
+  constexpr int PLB = HH * HW * PXB, IMGB = NP * PLB;   // bytes per plane, per image
+  constexpr int LDSB = STG ? 2 * IMGB : NP * PL * 16;
+  __shared__ uint4 Xs[LDSB / 16];
+  char* const xlds = reinterpret_cast<char*>(Xs);
 
   auto xrow = [](int ci) { return ci ^ ((ci >> 2) & 2); };
   auto xoct = [](int ci) { return (ci >> 4) & 1; };
@@ -3250,9 +3280,11 @@ __global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1) void conv_wg
   // ---- x halo slots (channel quad fastest: coalesced 16-B lanes of one pixel)
   const int xcq = tid % (CIB / 4);
   const bool xc_ok = ci0 + 4 * xcq < a.kc;
-  // slot q: channel quad (fastest: coalesced), pixel octet half, shift s, halo row hy; it
-  // loads the 8 pixels its shifted copy needs and writes 4 channel rows x 3 planes
-  float4 xv[XS][8];
+  // STG 0 slot q: channel quad (fastest: coalesced), pixel octet half, shift s, halo row hy;
+  // it loads the 8 pixels its shifted copy needs and writes 4 channel rows x 3 planes.
+  // STG 1 slot q: channel quad, halo pixel (hy, hx): one float4
+  constexpr int XE = STG ? 1 : 8;                  // pixels per slot
+  float4 xv[XS][XE];
   auto load_x = [&](int t) {
     const int b = t / (tiles_x * tiles_y);
     const int trem = t - b * tiles_x * tiles_y;
@@ -3261,24 +3293,45 @@ __global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1) void conv_wg
 #pragma unroll
     for (int j = 0; j < XS; ++j) {
       const int q = tid + NT * j;
-      const int r2 = q / (CIB / 4);
-      const int half = r2 & 1, s = (r2 >> 1) % KS, hy = (r2 >> 1) / KS;
-      const int iy = iy0 + hy;
-      const bool rok = q < XQ && xc_ok && (unsigned)iy < (unsigned)a.h;
-      const int ix0 = ix00 + 8 * half + s;
-      const int base = ((b * a.h + iy) * a.w + ix0) * a.lda + ci0 + 4 * xcq;
+      if constexpr (STG == 1) {
+        const int hp = q / (CIB / 4);
+        const int hy = hp / HW, hx = hp - hy * HW;
+        const int iy = iy0 + hy, ix = ix00 + hx;
+        const bool ok = q < XQ && xc_ok && (unsigned)iy < (unsigned)a.h &&
+                        (unsigned)ix < (unsigned)a.w;
+        const int base = ((b * a.h + iy) * a.w + ix) * a.lda + ci0 + 4 * xcq;
+        xv[j][0] = bload4(rx, ok ? (uint32_t)(base * 4) : kOOB);
+      } else {
+        const int r2 = q / (CIB / 4);
+        const int half = r2 & 1, s = (r2 >> 1) % KS, hy = (r2 >> 1) / KS;
+        const int iy = iy0 + hy;
+        const bool rok = q < XQ && xc_ok && (unsigned)iy < (unsigned)a.h;
+        const int ix0 = ix00 + 8 * half + s;
+        const int base = ((b * a.h + iy) * a.w + ix0) * a.lda + ci0 + 4 * xcq;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const bool ok = rok && (unsigned)(ix0 + e) < (unsigned)a.w;
-        xv[j][e] = bload4(rx, ok ? (uint32_t)((base + e * a.lda) * 4) : kOOB);
+        for (int e = 0; e < 8; ++e) {
+          const bool ok = rok && (unsigned)(ix0 + e) < (unsigned)a.w;
+          xv[j][e] = bload4(rx, ok ? (uint32_t)((base + e * a.lda) * 4) : kOOB);
+        }
       }
     }
   };
-  auto store_x = [&]() {
-#pragma unroll
-    for (int j = 0; j < XS; ++j) {
-      const int q = tid + NT * j;
-      if (q < XQ) {
+  // STG 0: slot j into the one halo; STG 1: slot j into image `buf` (4 channels of one pixel:
+  // 8 bytes per plane, as the 9-tap form's)
+  auto store_x = [&](int j, int buf) {
+    const int q = tid + NT * j;
+    if (XQ % NT == 0 || q < XQ) {
+      if constexpr (STG == 1) {
+        const int hp = q / (CIB / 4);
+        const int hx = hp % HW;
+        char* dst = xlds + buf * IMGB + hp * PXB + (((xcq >> 2) ^ wgx3b_sw<CIB>(hx)) << 5) +
+                    8 * (xcq & 3);
+        uint2 h, m, l;
+        split3x4(xv[j][0], h, m, l);
+        *reinterpret_cast<uint2*>(dst) = h;
+        *reinterpret_cast<uint2*>(dst + PLB) = m;
+        *reinterpret_cast<uint2*>(dst + 2 * PLB) = l;
+      } else {
         const int r2 = q / (CIB / 4);
         const int half = r2 & 1, s = (r2 >> 1) % KS, hy = (r2 >> 1) / KS;
         const int ci = 4 * xcq;
@@ -3297,6 +3350,10 @@ __global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1) void conv_wg
         }
       }
     }
+  };
+  auto store_x_all = [&](int buf) {
+#pragma unroll
+    for (int j = 0; j < XS; ++j) store_x(j, buf);
   };
   // ---- dy fragment of this lane: output channel co, pixels 8 lk .. 8 lk + 7 of tile row kk
   const int co = co0 + wco0 + lrow;
@@ -3333,19 +3390,44 @@ __global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1) void conv_wg
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
   const int a_base = xrow(wci0 + lrow) * 2 + (lk ^ xoct(wci0 + lrow));
+  // STG 1: the same fragment by two transposing reads per plane.  The lane's 16-lane group
+  // g = lane >> 4 reads the pixels 8 lk + s + 4 h .. + 3 (h = 0, 1) of halo row kk + wr x the
+  // channels wci0 + 16 (g & 1) .. + 15; lane 4 q + p of the group gives the address of pixel q,
+  // channels 4 p .. 4 p + 3 and lane l16 receives its channel's four pixels.  Byte offsets per
+  // (s, h) (the swizzle depends on the pixel); the tile row and the plane are immediate offsets.
+  int a_tr[KS][2];
+  if constexpr (STG == 1) {
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int hx = 8 * lk + s + 4 * h + ((lane >> 2) & 3);
+        a_tr[s][h] = (wr * HW + hx) * PXB +
+                     ((((wci0 >> 4) + ((lane >> 4) & 1)) ^ wgx3b_sw<CIB>(hx)) << 5) + 8 * (lane & 3);
+      }
+  }
   float colacc = 0.f;
   float dcur[8], dnext[8];
 
   if (steps > 0) {
     load_x(t_begin);
     load_dy(dcur, t_begin, 0);
-    store_x();
+    store_x_all(0);
   }
   __syncthreads();
   for (int i = 0; i < steps; ++i) {
     const int t = t_begin + i;
     const bool more = i + 1 < steps;
     if (more) load_x(t + 1);
+    // STG 1: tile i is read from image i & 1 while tile i + 1 goes into the other one
+    const int buf = STG ? i & 1 : 0;
+    int a_cur[KS][2];
+    if constexpr (STG == 1) {
+#pragma unroll
+      for (int s = 0; s < KS; ++s)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) a_cur[s][h] = a_tr[s][h] + buf * IMGB;
+    }
 #pragma unroll
     for (int kk = 0; kk < XH; ++kk) {
       if (kk + 1 < XH) load_dy(dnext, t, kk + 1);
@@ -3360,9 +3442,17 @@ __global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1) void conv_wg
       // A fragments one tap ahead of the MFMAs (bounded register footprint)
       bf16x8 fa[2][NP];
       auto load_a = [&](bf16x8 (&f)[NP], int s) {
-        const int xa = (s * HH + kk + wr) * CIB * 2 + a_base;
+        if constexpr (STG == 1) {
 #pragma unroll
-        for (int p = 0; p < NP; ++p) f[p] = __builtin_bit_cast(bf16x8, Xs[p * PL + xa]);
+          for (int p = 0; p < NP; ++p) {
+            const int ro = p * PLB + kk * HW * PXB;
+            f[p] = tr_frag(xlds, a_cur[s][0] + ro, a_cur[s][1] + ro);
+          }
+        } else {
+          const int xa = (s * HH + kk + wr) * CIB * 2 + a_base;
+#pragma unroll
+          for (int p = 0; p < NP; ++p) f[p] = __builtin_bit_cast(bf16x8, Xs[p * PL + xa]);
+        }
       };
       load_a(fa[0], 0);
 #pragma unroll
@@ -3381,10 +3471,22 @@ __global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1) void conv_wg
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) dcur[e] = dnext[e];
+      if constexpr (STG == 1) {
+        // the next tile's slots, spread over the k-steps: the split runs beside the SIMD's
+        // other waves' MFMAs, and nobody reads that image before the barrier below
+        if (more) {
+#pragma unroll
+          for (int j = 0; j < XS; ++j)
+            if (j * XH / XS == kk) store_x(j, buf ^ 1);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
     __syncthreads();              // every wave is done with this tile's halo
-    if (more) store_x();
-    __syncthreads();
+    if constexpr (STG == 0) {
+      if (more) store_x_all(0);
+      __syncthreads();
+    }
   }
 
   // ---- raw partial sums into this K slice's slab (+ bias column sums in row M)
@@ -3402,6 +3504,16 @@ __global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1) void conv_wg
         if (ci < a.kc) S[((int64_t)(wr * KS + s) * a.kc + ci) * a.slab_ld + co] = acc[s][r];
       }
   }
+}
+
+template <int WAVES_CI, int WAVES_CO, int WAVES_R, int XH>
+__global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1) void conv_wgrad_tile_x3(GemmArgs a) {
+  wgrad_x3_body<WAVES_CI, WAVES_CO, WAVES_R, XH, 1>(a);
+}
+// The same on the three shifted halo copies (of_set_tuning key 40 = 0): bitwise the same sums.
+template <int WAVES_CI, int WAVES_CO, int WAVES_R, int XH>
+__global__ __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1) void conv_wgrad_tile_x3_c3(GemmArgs a) {
+  wgrad_x3_body<WAVES_CI, WAVES_CO, WAVES_R, XH, 0>(a);
 }
 
 // ---- conv_wgrad_tile_x3b: the same weight gradient with all 9 taps per wave ---------------
@@ -3435,15 +3547,8 @@ __device__ __forceinline__ int wgx3b_slot(int ci, int oct) {
 }
 
 // The body is shared with the bf16 weight gradient (NP = 1: x and dy rounded to bf16 RNE, one
-// plane, one MFMA per fragment pair); NP = 3 is the fp32 split.
-// Swizzle of the pixel-major image's 32-byte channel blocks by the halo column hx: bit 3 of hx
-// moves the two 16-lane groups of a half (pixels 8 apart) to different blocks; on 128-byte
-// pixel rows (CIB = 64) bit 1 of hx moves the rows 2 apart of one group (256 bytes) as well.
-template <int CIB>
-__device__ __forceinline__ int wgx3b_sw(int hx) {
-  return ((hx >> 3) & 1) | (CIB == 64 ? ((hx >> 1) & 1) << 1 : 0);
-}
-
+// plane, one MFMA per fragment pair); NP = 3 is the fp32 split.  (wgx3b_sw: above the 3-tap
+// form, which stages the same image.)
 template <int WAVES_CI, int WAVES_CO, int XH, int MI, int NP, int STG>
 __device__ __forceinline__ void wgrad_x3b_body(const GemmArgs& a) {
   constexpr int NJ = 2 / MI;
@@ -4941,15 +5046,18 @@ bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static int g_vec_ep = 1;   // of_set_tuning key 3 (0: per-element epilogue, for A/B and tests)
 // of_set_tuning key 4: conv_wgrad_tile_x3b for Cout % 128 == 0 (1, default), for every
 // x3 weight gradient (2), or never (0: the 3-tap form).  Measured per layer (same box): the
-// 9-tap form +6-11 % on the Cout = 128 layers, even on Cout 96 / 64, -6 % on Cout 32.
+// 9-tap form +6-11 % on the Cout = 128 layers.  With both forms on the halo image (key 40,
+// profiles/wgrad3_stage_ab.md): +7 % on Cout 96 (dec3.c2; not yet its default), even on
+// Cout 64, -9 % on Cout 32.
 static int g_wgx3b = 1;
 // of_set_tuning key 5: conv_wgrad_tile_x3b wave shape, 16 MI ci x 32 / MI co (MI = 1 or 2).
 // MI = 2 halves the dy loads and splits per MFMA and measured the same (dec3.c1 0.516 vs
 // 0.517 ms): the split VALU is not what bounds the kernel.
 static int g_wgx3b_mi = 1;
-// of_set_tuning key 40: the 9-tap weight gradients' x halo (conv_wgrad_tile_x3b / _b16) as one
-// pixel-major image read with transposing LDS reads, double-buffered (1, default), or as
-// three pixel-shifted copies, single-buffered (0: the _c3 kernels; bitwise the same sums).
+// of_set_tuning key 40: the 3-tap and 9-tap weight gradients' x halo (conv_wgrad_tile_x3 / _x3b
+// / _b16) as one pixel-major image read with transposing LDS reads, double-buffered (1,
+// default), or as three pixel-shifted copies, single-buffered (0: the _c3 kernels; bitwise the
+// same sums).
 static int g_wgx3b_stage = 1;
 // of_set_tuning key 33: at least this many K tiles per split-K slice of the 9-tap weight
 // gradients (conv_wgrad_tile_x3b / _b16).  Every slice writes a 9 x cin x cout fp32 slab that
@@ -5542,11 +5650,12 @@ constexpr Launch wgrad_stem_rec() {
   return {conv_wgrad_stem_x3<NP, FUSED>, SW_NT, NP == 1 ? KIND_STEM_WG_B16 : KIND_STEM_WG_X3,
           FUSED ? "conv_wgrad_stem_x3 fused" : "conv_wgrad_stem_x3"};
 }
-// conv_wgrad_tile_x3: __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1)
-template <int CI, int CO, int R, int XH>
+// conv_wgrad_tile_x3 and its _c3 form: __launch_bounds__(64 * WAVES_CI * WAVES_CO * WAVES_R, 1);
+// STAGE is of_set_tuning key 40 (0: the _c3 kernel)
+template <int STAGE, int CI, int CO, int R, int XH>
 constexpr Launch wgrad_tile_x3_rec() {
-  return {conv_wgrad_tile_x3<CI, CO, R, XH>, 64 * CI * CO * R, kind(KIND_TILE_X3, MODE_WGRAD, 0),
-          "conv_wgrad_tile_x3"};
+  return {STAGE ? conv_wgrad_tile_x3<CI, CO, R, XH> : conv_wgrad_tile_x3_c3<CI, CO, R, XH>,
+          64 * CI * CO * R, kind(KIND_TILE_X3, MODE_WGRAD, 0), "conv_wgrad_tile_x3"};
 }
 // conv_wgrad_tile_x3b / _b16 and their _c3 forms: __launch_bounds__(64 * WAVES_CI * WAVES_CO, 1);
 // STAGE is of_set_tuning key 40 (0: the _c3 kernels)
@@ -5571,7 +5680,7 @@ constexpr Launch wgrad_tile_f32_rec() {
 }
 
 // fp32 3x3 stride-1 weight gradient by wgx3_cfg: the 9-tap form (key 4) [key 40][key 5 - 1][cfg]
-// with waves of 16 MI ci x 32 / MI co, or the 3-tap form (cfg 0-3).
+// with waves of 16 MI ci x 32 / MI co, or the 3-tap form [key 40][cfg 0-3].
 Launch wgrad_tile_x3_launch(int cfg) {
   static const Launch B[2][2][5] = {
       {{wgrad_x3b_rec<0, 2, 4, 8>(), wgrad_x3b_rec<0, 2, 3, 8>(), wgrad_x3b_rec<0, 4, 2, 4>(),
@@ -5582,10 +5691,13 @@ Launch wgrad_tile_x3_launch(int cfg) {
         wgrad_x3b_rec<1, 4, 1, 4>(), wgrad_x3b_rec<1, 2, 2, 8>()},
        {wgrad_x3b_rec<1, 1, 8, 8, 2>(), wgrad_x3b_rec<1, 1, 6, 8, 2>(), wgrad_x3b_rec<1, 2, 4, 4, 2>(),
         wgrad_x3b_rec<1, 2, 2, 4, 2>(), wgrad_x3b_rec<1, 1, 4, 8, 2>()}}};
-  static const Launch T[4] = {wgrad_tile_x3_rec<1, 4, 3, 8>(), wgrad_tile_x3_rec<1, 3, 3, 8>(),
-                              wgrad_tile_x3_rec<2, 2, 3, 4>(), wgrad_tile_x3_rec<2, 1, 3, 4>()};
+  static const Launch T[2][4] = {
+      {wgrad_tile_x3_rec<0, 1, 4, 3, 8>(), wgrad_tile_x3_rec<0, 1, 3, 3, 8>(),
+       wgrad_tile_x3_rec<0, 2, 2, 3, 4>(), wgrad_tile_x3_rec<0, 2, 1, 3, 4>()},
+      {wgrad_tile_x3_rec<1, 1, 4, 3, 8>(), wgrad_tile_x3_rec<1, 1, 3, 3, 8>(),
+       wgrad_tile_x3_rec<1, 2, 2, 3, 4>(), wgrad_tile_x3_rec<1, 2, 1, 3, 4>()}};
   const bool x3b = g_wgx3b == 2 || (g_wgx3b == 1 && cfg == 0) || cfg == 4;
-  return with_cfg(x3b ? B[g_wgx3b_stage][g_wgx3b_mi - 1][cfg] : T[cfg], cfg);
+  return with_cfg(x3b ? B[g_wgx3b_stage][g_wgx3b_mi - 1][cfg] : T[g_wgx3b_stage][cfg], cfg);
 }
 // bf16 on the 9-tap structure (key 13): the x3b configurations, [key 40][cfg]
 Launch wgrad_tile_b16_launch(int cfg) {
