@@ -461,6 +461,57 @@ int of_census_bwd_multi(const float* const* dcdfs, int n, const int* hs, const i
                         int levels, const float* coefs, const float* dloss,
                         float* const* dflows, const int* lds, int accumulate, void* stream);
 
+/* Occlusion masks (image convention only: a reference-convention flow is not a displacement),
+ * every level in one launch (levels <= 8; flows[l] is (n,hs[l],ws[l],2), 8-byte aligned, and
+ * masks[l] dense (n,hs[l],ws[l]) floats, every one written, exactly 0.0f or 1.0f).  Per pixel
+ * (b,i,j) with f = flows[l][b,i,j] and the sample point x = j + f0, y = i + f1 formed in fp32
+ * exactly as the OF_WARP_IMAGE sampler forms it:
+ *   OF_OCC_BORDER: mask = 1 iff 0 <= x <= w-1 and 0 <= y <= h-1 (inclusive: a sample exactly
+ *     on the last column or the first row is valid).  pair_stride and alpha2s are not read and
+ *     any n >= 1 is accepted.
+ *   OF_OCC_FB (forward-backward consistency): n == 2 * pair_stride; images [0,B) hold the
+ *     forward flows and [B,2B) the flows of the same pairs with the two images exchanged, so
+ *     image b's partner is (b + pair_stride) % n.  With g~ the partner's flow (both channels)
+ *     sampled at (x, y) by the OF_WARP_IMAGE bilinear sampler,
+ *       mask = 1 iff the border condition holds and
+ *                    |f + g~|^2 <= alpha1 * (|f|^2 + |g~|^2) + alpha2s[l].
+ *     alpha2s[l] is in squared pixels of level l's own grid.
+ * The mask is a constant of the loss: nothing differentiates through it.  Pixelwise, no
+ * atomics, no allocation, no host sync.  OF_EINVAL (and no launch) for levels outside 1..8, n,
+ * h or w < 1, an unknown mode, OF_OCC_FB with n != 2 * pair_stride or pair_stride < 1,
+ * alpha1 < 0, NULL or negative alpha2s[l] with OF_OCC_FB, NULL flows or masks (or an entry). */
+#define OF_OCC_BORDER 1
+#define OF_OCC_FB 2
+int of_occ_mask_multi(const float* const* flows, int n, int pair_stride, const int* hs,
+                      const int* ws, int levels, int mode, float alpha1, const float* alpha2s,
+                      float* const* masks, void* stream);
+
+/* The multi-level data terms with a per-pixel weight (an occlusion mask, or any non-negative
+ * float): weights[l] is dense (n,hs[l],ws[l]); a NULL `weights`, or a NULL weights[l], is
+ * weight 1 for every pixel (of that level).  The weights are constants.  Everything else is
+ * the argument of the `_cv` form of the same name, and with all weights 1 (or NULL) the
+ * results are bitwise those of the `_cv` form.
+ *   photometric forward: pixel p adds weights[l][p] * sum_c |diff[p,c]| to its block's partial;
+ *   photometric backward: d(flow)[p] is weights[l][p] times the unweighted d(flow)[p];
+ *   census forward: the weight multiplies the centre pixel's window sum,
+ *       C_l = (1/K) sum_p w[p] sum_o phi(e[p,o]),
+ *     and the plane is d C_l / d flow of that:  d C_l / d u[q] = (1/K) sum_o (w[q] + w[q+o])
+ *     phi'(e[q,o]) tau'(u[q+o] - u[q])  (every unordered pair appears once from each end, with
+ *     the same value), times d u[q] / d flow.  of_census_bwd_multi scales the plane as before.
+ * The normalisers stay the caller's coefs (means over all n*h*w pixels): a pixel of weight 0
+ * counts as zero error. */
+int of_photo_l1_fwd_multi_w(const float* const* img6s, const float* const* flows,
+                            const float* const* weights, int n, const int* hs, const int* ws,
+                            int levels, float* partials, int convention, void* stream);
+int of_photo_l1_bwd_multi_w(const float* const* img6s, const float* const* flows,
+                            const float* const* weights, int n, const int* hs, const int* ws,
+                            int levels, const float* coefs, const float* dloss,
+                            float* const* dflows, const int* lds, int convention, void* stream);
+int of_census_fwd_multi_w(const float* const* img6s, const float* const* flows,
+                          const float* const* weights, int n, const int* hs, const int* ws,
+                          int levels, int radius, const float* coefs, float* const* workspaces,
+                          float* const* dcdfs, float* partials, int convention, void* stream);
+
 /* Keras Adam (train.py:34,56; P13), one launch over a flat parameter arena, g' = g*gscale
  * (gscale folds the 1/world of a data-parallel gradient average):
  * m += (g'-m)(1-b1); v += (g'^2-v)(1-b2); p -= lr_t * m / (sqrt(v) + eps). */

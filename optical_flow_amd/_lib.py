@@ -18,6 +18,7 @@ OF_OK, OF_EINVAL, OF_EHIP, OF_EUNSUPPORTED, OF_ETIMEOUT = 0, 1, 2, 3, 4
 OF_REDUCE_SUM, OF_REDUCE_AVG = 0, 1         # of_comm_allreduce_ex_async op
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 WARP_REFERENCE, WARP_IMAGE = 0, 1           # OF_WARP_REFERENCE / OF_WARP_IMAGE of the _cv entries
+OCC_BORDER, OCC_FB = 1, 2                   # OF_OCC_BORDER / OF_OCC_FB of of_occ_mask_multi
 
 
 class B16iIO(C.Structure):
@@ -201,6 +202,18 @@ PROTOTYPES = {
                                    C.POINTER(F), C.POINTER(P), C.POINTER(P), P, I, P]),
     "of_census_bwd_multi": (I, [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I, C.POINTER(F), P,
                                 C.POINTER(P), C.POINTER(I), I, P]),
+    # occlusion masks (OCC_BORDER / OCC_FB) and the data terms weighted by them: the `_cv`
+    # forms with the per-level weights after the flows
+    "of_occ_mask_multi": (I, [C.POINTER(P), I, I, C.POINTER(I), C.POINTER(I), I, I, F,
+                              C.POINTER(F), C.POINTER(P), P]),
+    "of_photo_l1_fwd_multi_w": (I, [C.POINTER(P), C.POINTER(P), C.POINTER(P), I, C.POINTER(I),
+                                    C.POINTER(I), I, P, I, P]),
+    "of_photo_l1_bwd_multi_w": (I, [C.POINTER(P), C.POINTER(P), C.POINTER(P), I, C.POINTER(I),
+                                    C.POINTER(I), I, C.POINTER(F), P, C.POINTER(P), C.POINTER(I),
+                                    I, P]),
+    "of_census_fwd_multi_w": (I, [C.POINTER(P), C.POINTER(P), C.POINTER(P), I, C.POINTER(I),
+                                  C.POINTER(I), I, I, C.POINTER(F), C.POINTER(P), C.POINTER(P), P,
+                                  I, P]),
     "of_stem_bwd_fused_workspace": (SZ, [PD, I]),
     "of_stem_bwd_fused": (I, [PD, I, P, I, P, P, P, P, P, P, F, P, P, P, P, I, P, SZ, P]),
     # BatchNormalization in training mode (bn_mode="training")

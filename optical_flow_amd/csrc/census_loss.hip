@@ -78,13 +78,25 @@ __device__ __forceinline__ float census_tau(float d, float r) {
   return d * r;
 }
 
-template <int R, int CV>
+// Per-level pixel weights of of_census_fwd_multi_w ((n,h,w) floats; NULL: weight 1).
+struct CensusWeights {
+  const float* w[8];
+};
+
+// WT: the weighted form, C = (1/K) sum_p w[p] sum_o phi(e[p,o]).  A pair {q, q+o} is counted
+// once from each end with the same value (tau odd, phi even), now with the weights w[q] and
+// w[q+o]: dC/du[q] = (1/K) sum_o (w[q] + w[q+o]) phi'(e[q,o]) tau'(u[q+o] - u[q]), still a
+// gather from the tile, which holds w for its halo too.  A template parameter so that the
+// unweighted instantiations stay the code they were.
+template <int R, int CV, bool WT = false>
 __global__ __launch_bounds__(CN_THREADS) void census_fwd_multi(CensusMulti m,
-                                                               float* __restrict__ partials) {
+                                                               float* __restrict__ partials,
+                                                               CensusWeights wt = {}) {
   constexpr int HW = CN_TX + 2 * R, HH = CN_TY + 2 * R;
   constexpr float INV_K = 1.f / (float)((2 * R + 1) * (2 * R + 1) - 1);
   __shared__ float2 s_gu[HH * HW];      // (g1, u); 0 outside the image (never used: masked)
   __shared__ float2 s_du[HH * HW];      // du/d(flow), read at the tile's own pixels only
+  __shared__ float s_w[WT ? HH * HW : 1];   // WT: the weights; 0 outside the image
   __shared__ float red[CN_THREADS / 64];
 
   int l = 0;
@@ -105,6 +117,12 @@ __global__ __launch_bounds__(CN_THREADS) void census_fwd_multi(CensusMulti m,
     if (y >= 0 && y < h && x >= 0 && x < w) census_sample<CV>(img6, flow, y, x, h, w, img, gu, du);
     s_gu[k] = gu;
     s_du[k] = du;
+    if (WT) {
+      float wv = 0.f;
+      if (y >= 0 && y < h && x >= 0 && x < w)
+        wv = wt.w[l] ? wt.w[l][img + (int64_t)y * w + x] : 1.f;
+      s_w[k] = wv;
+    }
   }
   __syncthreads();
 
@@ -113,6 +131,7 @@ __global__ __launch_bounds__(CN_THREADS) void census_fwd_multi(CensusMulti m,
   const bool live = y < h && x < w;
   const int c = (ly + R) * HW + lx + R;
   const float2 ctr = s_gu[c];
+  const float wc = WT ? s_w[c] : 1.f;
   float s = 0.f, g = 0.f;
   // one window row per iteration: unrolled over all (2R+1)^2 taps the compiler holds every
   // LDS read of the window in flight (227 VGPRs at R = 3, 2 waves per SIMD)
@@ -131,11 +150,16 @@ __global__ __launch_bounds__(CN_THREADS) void census_fwd_multi(CensusMulti m,
       const float inv = __builtin_amdgcn_rcpf(CN_CD + e2);
       // phi(e) and phi'(e) * tau'(d2) = (2 c_d e / (c_d + e^2)^2) * (c_t / (c_t + d2^2)^1.5)
       s += ok ? e2 * inv : 0.f;
-      g += ok ? (e * inv * inv) * (r2 * r2 * r2) : 0.f;
+      if (WT)
+        g += ok ? (wc + s_w[c + dy * HW + dx]) * ((e * inv * inv) * (r2 * r2 * r2)) : 0.f;
+      else
+        g += ok ? (e * inv * inv) * (r2 * r2 * r2) : 0.f;
     }
   }
+  if (WT) s *= wc;      // the centre's weight on its window sum
   if (m.dcdf[l] && live) {
-    const float dcdu = g * (2.f * CN_CD * CN_CT * 2.f * INV_K);
+    // unweighted: both ends of a pair give the same term, the 2 of it is in the constant
+    const float dcdu = g * (WT ? 2.f * CN_CD * CN_CT * INV_K : 2.f * CN_CD * CN_CT * 2.f * INV_K);
     const float2 du = s_du[c];
     *reinterpret_cast<float2*>(m.dcdf[l] + 2 * (img + (int64_t)y * w + x)) =
         make_float2(dcdu * du.x, dcdu * du.y);
@@ -216,6 +240,14 @@ int of_census_fwd_multi_cv(const float* const* img6s, const float* const* flows,
                            const int* hs, const int* ws, int levels, int radius,
                            const float* coefs, float* const* workspaces, float* const* dcdfs,
                            float* partials, int convention, void* stream) {
+  return of_census_fwd_multi_w(img6s, flows, nullptr, n, hs, ws, levels, radius, coefs,
+                               workspaces, dcdfs, partials, convention, stream);
+}
+
+int of_census_fwd_multi_w(const float* const* img6s, const float* const* flows,
+                          const float* const* weights, int n, const int* hs, const int* ws,
+                          int levels, int radius, const float* coefs, float* const* workspaces,
+                          float* const* dcdfs, float* partials, int convention, void* stream) {
   static const std::string fn = "of_census_fwd_multi";
   if (convention != OF_WARP_REFERENCE && convention != OF_WARP_IMAGE)
     return fail(OF_EINVAL, fn + ": unknown warp convention");
@@ -244,10 +276,23 @@ int of_census_fwd_multi_cv(const float* const* img6s, const float* const* flows,
   if (m.beg[levels] >= INT32_MAX) return fail(OF_EINVAL, fn + ": too many blocks");
   const dim3 grid((unsigned)m.beg[levels]), block(CN_THREADS);
   const bool im = convention == OF_WARP_IMAGE;
+  CensusWeights wt{};
+  bool weighted = false;          // a NULL array or only NULL entries: the unweighted kernel
+  for (int l = 0; l < levels; ++l) {
+    wt.w[l] = weights ? weights[l] : nullptr;
+    weighted = weighted || wt.w[l];
+  }
+  if (weighted) {
+    auto kw = radius == 1   ? (im ? census_fwd_multi<1, WARP_CV_IMAGE, true> : census_fwd_multi<1, WARP_CV_REFERENCE, true>)
+              : radius == 2 ? (im ? census_fwd_multi<2, WARP_CV_IMAGE, true> : census_fwd_multi<2, WARP_CV_REFERENCE, true>)
+                            : (im ? census_fwd_multi<3, WARP_CV_IMAGE, true> : census_fwd_multi<3, WARP_CV_REFERENCE, true>);
+    hipLaunchKernelGGL(kw, grid, block, 0, as_stream(stream), m, partials, wt);
+    return check_launch("census_fwd_multi_w");
+  }
   auto k = radius == 1   ? (im ? census_fwd_multi<1, WARP_CV_IMAGE> : census_fwd_multi<1, WARP_CV_REFERENCE>)
            : radius == 2 ? (im ? census_fwd_multi<2, WARP_CV_IMAGE> : census_fwd_multi<2, WARP_CV_REFERENCE>)
                          : (im ? census_fwd_multi<3, WARP_CV_IMAGE> : census_fwd_multi<3, WARP_CV_REFERENCE>);
-  hipLaunchKernelGGL(k, grid, block, 0, as_stream(stream), m, partials);
+  hipLaunchKernelGGL(k, grid, block, 0, as_stream(stream), m, partials, wt);
   return check_launch("census_fwd_multi");
 }
 

@@ -1728,9 +1728,25 @@ struct PhotoMulti {
   int64_t beg[9];
   int levels;
 };
-template <int CV>
+// photo_sample's bilinear sum of one channel with every product and sum rounded on its own
+// (no fma): see photo_l1_fwd_multi<CV, true>.
+__device__ __forceinline__ float photo_warp_unfused(float a, float b, float v0, float v1,
+                                                    float v2, float v3) {
+#pragma clang fp contract(off)
+  const float w00 = a * b, w01 = a * (1.f - b), w10 = (1.f - a) * b,
+              w11 = (1.f - a) * (1.f - b);
+  return w00 * v0 + w01 * v1 + w10 * v2 + w11 * v3;
+}
+
+// Per-level pixel weights of the `_w` entry points ((n,h,w) floats; NULL: weight 1).  WT is a
+// template parameter so that the unweighted instantiations stay the code they were.
+struct PhotoWeights {
+  const float* w[8];
+};
+template <int CV, bool WT = false>
 __global__ __launch_bounds__(PL_THREADS) void photo_l1_fwd_multi(int n, PhotoMulti m,
-                                                                 float* __restrict__ partials) {
+                                                                 float* __restrict__ partials,
+                                                                 PhotoWeights wt = {}) {
   int l = 0;
   while (l + 1 < m.levels && (int64_t)blockIdx.x >= m.beg[l + 1]) ++l;
   const int h = m.h[l], w = m.w[l];
@@ -1749,7 +1765,19 @@ __global__ __launch_bounds__(PL_THREADS) void photo_l1_fwd_multi(int n, PhotoMul
     float diff[3], v[4][3];
     WarpTap t;
     photo_sample<CV>(img6, p, i, j, flow[2 * p], flow[2 * p + 1], h, w, img, diff, t, v);
-    s += fabsf(diff[0]) + fabsf(diff[1]) + fabsf(diff[2]);
+    if (WT) {
+      // Weight 1 must give the unweighted instantiation's partials bit for bit.  There the
+      // compiler sums channel 2's warp from four separately rounded products (it pairs the
+      // products into packed multiplies) and channels 0 and 1 by an fma chain; here, left to
+      // itself, it contracts channel 2 as well.  So channel 2 is formed with the roundings
+      // pinned (tests/test_gpu_occlusion.py compares the two bitwise).
+      const float d2 = img6[p * 6 + 2] - photo_warp_unfused(t.a, t.b, v[0][2], v[1][2], v[2][2],
+                                                            v[3][2]);
+      const float wp = wt.w[l] ? wt.w[l][p] : 1.f;
+      s += wp * (fabsf(diff[0]) + fabsf(diff[1]) + fabsf(d2));
+    } else {
+      s += fabsf(diff[0]) + fabsf(diff[1]) + fabsf(diff[2]);
+    }
   }
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
   __shared__ float red[PL_THREADS / 64];
@@ -1762,9 +1790,10 @@ __global__ __launch_bounds__(PL_THREADS) void photo_l1_fwd_multi(int n, PhotoMul
   }
 }
 
-template <int CV>
+template <int CV, bool WT = false>
 __global__ __launch_bounds__(256) void photo_l1_bwd_multi(int n, PhotoMulti m,
-                                                          const float* __restrict__ dloss) {
+                                                          const float* __restrict__ dloss,
+                                                          PhotoWeights wt = {}) {
   const int64_t total = m.beg[m.levels];
   const float dl = dloss ? dloss[0] : 1.f;
   for (int64_t gp = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; gp < total;
@@ -1790,6 +1819,11 @@ __global__ __launch_bounds__(256) void photo_l1_bwd_multi(int n, PhotoMulti m,
       const float g = -coef * sg;
       gx -= g * (b * (v[0][e] - v[2][e]) + (1.f - b) * (v[1][e] - v[3][e]));
       gy -= g * (a * (v[0][e] - v[1][e]) + (1.f - a) * (v[2][e] - v[3][e]));
+    }
+    if (WT) {
+      const float wp = wt.w[l] ? wt.w[l][p] : 1.f;
+      gx *= wp;
+      gy *= wp;
     }
     m.dflow[l][m.ld[l] * p] = gx;
     m.dflow[l][m.ld[l] * p + 1] = gy;
@@ -2296,9 +2330,27 @@ int of_photo_l1_fwd_multi(const float* const* img6s, const float* const* flows, 
                                   stream);
 }
 
+// The weights of the levels as a kernel argument; false when every level has weight 1 (a NULL
+// array or only NULL entries): the caller then launches the unweighted instantiation.
+static bool photo_weights(const float* const* weights, int levels, PhotoWeights& wt) {
+  bool any = false;
+  for (int l = 0; l < levels; ++l) {
+    wt.w[l] = weights ? weights[l] : nullptr;
+    any = any || wt.w[l];
+  }
+  return any;
+}
+
 int of_photo_l1_fwd_multi_cv(const float* const* img6s, const float* const* flows, int n,
                              const int* hs, const int* ws, int levels, float* partials,
                              int convention, void* stream) {
+  return of_photo_l1_fwd_multi_w(img6s, flows, nullptr, n, hs, ws, levels, partials, convention,
+                                 stream);
+}
+
+int of_photo_l1_fwd_multi_w(const float* const* img6s, const float* const* flows,
+                            const float* const* weights, int n, const int* hs, const int* ws,
+                            int levels, float* partials, int convention, void* stream) {
   OF_CHECK_ARG(convention == OF_WARP_REFERENCE || convention == OF_WARP_IMAGE,
                "photo l1 fwd multi: unknown warp convention");
   OF_CHECK_ARG(img6s && flows && hs && ws && partials && levels >= 1 && levels <= 8,
@@ -2314,10 +2366,18 @@ int of_photo_l1_fwd_multi_cv(const float* const* img6s, const float* const* flow
     m.w[l] = ws[l];
     m.beg[l + 1] = m.beg[l] + of_photo_l1_partials(n, hs[l], ws[l]);
   }
+  PhotoWeights wt{};
+  if (photo_weights(weights, levels, wt)) {
+    auto kw = convention == OF_WARP_IMAGE ? photo_l1_fwd_multi<WARP_CV_IMAGE, true>
+                                          : photo_l1_fwd_multi<WARP_CV_REFERENCE, true>;
+    hipLaunchKernelGGL(kw, dim3((unsigned)m.beg[levels]), dim3(PL_THREADS), 0, as_stream(stream),
+                       n, m, partials, wt);
+    return check_launch("photo_l1_fwd_multi_w");
+  }
   hipLaunchKernelGGL(convention == OF_WARP_IMAGE ? photo_l1_fwd_multi<WARP_CV_IMAGE>
                                                  : photo_l1_fwd_multi<WARP_CV_REFERENCE>,
                      dim3((unsigned)m.beg[levels]), dim3(PL_THREADS), 0, as_stream(stream), n, m,
-                     partials);
+                     partials, wt);
   return check_launch("photo_l1_fwd_multi");
 }
 
@@ -2333,6 +2393,14 @@ int of_photo_l1_bwd_multi_cv(const float* const* img6s, const float* const* flow
                              const int* hs, const int* ws, int levels, const float* coefs,
                              const float* dloss, float* const* dflows, const int* lds,
                              int convention, void* stream) {
+  return of_photo_l1_bwd_multi_w(img6s, flows, nullptr, n, hs, ws, levels, coefs, dloss, dflows,
+                                 lds, convention, stream);
+}
+
+int of_photo_l1_bwd_multi_w(const float* const* img6s, const float* const* flows,
+                            const float* const* weights, int n, const int* hs, const int* ws,
+                            int levels, const float* coefs, const float* dloss,
+                            float* const* dflows, const int* lds, int convention, void* stream) {
   OF_CHECK_ARG(convention == OF_WARP_REFERENCE || convention == OF_WARP_IMAGE,
                "photo l1 bwd multi: unknown warp convention");
   OF_CHECK_ARG(img6s && flows && hs && ws && coefs && dflows && lds && levels >= 1 && levels <= 8,
@@ -2351,9 +2419,18 @@ int of_photo_l1_bwd_multi_cv(const float* const* img6s, const float* const* flow
     m.w[l] = ws[l];
     m.beg[l + 1] = m.beg[l] + (int64_t)n * hs[l] * ws[l];
   }
+  PhotoWeights wt{};
+  if (photo_weights(weights, levels, wt)) {
+    auto kw = convention == OF_WARP_IMAGE ? photo_l1_bwd_multi<WARP_CV_IMAGE, true>
+                                          : photo_l1_bwd_multi<WARP_CV_REFERENCE, true>;
+    hipLaunchKernelGGL(kw, dim3(grid_for(m.beg[levels])), dim3(256), 0, as_stream(stream), n, m,
+                       dloss, wt);
+    return check_launch("photo_l1_bwd_multi_w");
+  }
   hipLaunchKernelGGL(convention == OF_WARP_IMAGE ? photo_l1_bwd_multi<WARP_CV_IMAGE>
                                                  : photo_l1_bwd_multi<WARP_CV_REFERENCE>,
-                     dim3(grid_for(m.beg[levels])), dim3(256), 0, as_stream(stream), n, m, dloss);
+                     dim3(grid_for(m.beg[levels])), dim3(256), 0, as_stream(stream), n, m, dloss,
+                     wt);
   return check_launch("photo_l1_bwd_multi");
 }
 

@@ -25,13 +25,35 @@ class LossLayer:
     ``warp_convention`` (build-added): "reference" (default) warps image 2 on the reference's
     transposed grid (P1); "image" takes the flows as image-coordinate displacements (channel 0
     along x, channel 1 along y) in the photometric and the census term, so the true motion
-    brings the loss to zero.  It must be the net's (Trainer raises ValueError otherwise)."""
+    brings the loss to zero.  It must be the net's (Trainer raises ValueError otherwise).
+
+    ``occlusion`` (build-added, image convention only): "none" (default) scores every pixel;
+    "border" gives weight 0 in both data terms to the pixels whose sample point leaves the
+    frame (where the warp extrapolates); "fb" also to those that fail the forward-backward
+    consistency check |f + g~|^2 <= occlusion_alpha1 (|f|^2 + |g~|^2) + occlusion_alpha2
+    (alpha2 in squared full-resolution pixels), and must be called with the doubled batch
+    [pairs ; the same pairs with the two images exchanged] (Trainer.train_step forms it).  The
+    masks are computed from the flows as constants (ops.occlusion_masks; DESIGN.md "Occlusion
+    masks"); the means stay over all pixels and the smoothness term is not masked."""
 
     def __init__(self, smoothness_weight=0.0, edge_alpha=0.0, smoothness_eps=1e-4,
                  census_weight=0.0, census_radius=3, photometric_weight=1.0,
-                 warp_convention="reference"):
+                 warp_convention="reference", occlusion="none", occlusion_alpha1=0.01,
+                 occlusion_alpha2=0.5):
         ops.warp_convention(warp_convention)
         self.warp_convention = warp_convention
+        if occlusion not in ("none", "border", "fb"):
+            raise ValueError("occlusion must be 'none', 'border' or 'fb', got %r" % (occlusion,))
+        if not occlusion_alpha1 >= 0:
+            raise ValueError("occlusion_alpha1 must be >= 0, got %r" % (occlusion_alpha1,))
+        if not occlusion_alpha2 >= 0:
+            raise ValueError("occlusion_alpha2 must be >= 0, got %r" % (occlusion_alpha2,))
+        if occlusion != "none" and warp_convention != "image":
+            raise ValueError("occlusion=%r needs warp_convention='image': a %r-convention flow "
+                             "is not a displacement" % (occlusion, warp_convention))
+        self.occlusion = occlusion
+        self.occlusion_alpha1 = float(occlusion_alpha1)
+        self.occlusion_alpha2 = float(occlusion_alpha2)
         if not smoothness_weight >= 0:
             raise ValueError("smoothness_weight must be >= 0, got %r" % (smoothness_weight,))
         if not edge_alpha >= 0:
@@ -63,6 +85,18 @@ class LossLayer:
             assert flows[scale_idx].shape[1] == scaled_height
             assert flows[scale_idx].shape[2] == scaled_width
         assert batch_imgs.shape[3] == 6
+        if self.occlusion != "none":
+            if self.occlusion == "fb" and batch_imgs.shape[0] % 2:
+                raise ValueError("occlusion='fb' scores the doubled batch [pairs ; swapped "
+                                 "pairs]: an even number of images, got %d"
+                                 % batch_imgs.shape[0])
+            masks = ops.occlusion_masks([f.detach() for f in flows], self.occlusion,
+                                        self.occlusion_alpha1, self.occlusion_alpha2,
+                                        self.warp_convention)
+            return ops.census_flow_loss(batch_imgs, list(flows), self.census_weight,
+                                        self.census_radius, self.photometric_weight,
+                                        self.smoothness_weight, self.edge_alpha,
+                                        self.smoothness_eps, self.warp_convention, weights=masks)
         if self.census_weight == 0.0 and self.photometric_weight == 1.0:
             if self.smoothness_weight == 0.0:
                 return ops.photometric_loss(batch_imgs, list(flows), self.warp_convention)

@@ -2416,10 +2416,16 @@ def _census_coefs(n, hs, ws, scale):
     return [scale / (ns * n * h * w) for h, w in zip(hs, ws)]
 
 
-def _census_fwd(pyr, fl, radius, coefs, want_grad, wc=0):
+def _opt_ptrs(ts):
+    """A pointer array over tensors; None entries become NULL."""
+    return _arr(C.c_void_p, [t.data_ptr() if t is not None else None for t in ts])
+
+
+def _census_fwd(pyr, fl, radius, coefs, want_grad, wc=0, wts=None):
     """of_census_fwd_multi over every level: (partials, planes).  The partials sum to the
     weighted term (the coefficients are applied in the kernel); planes[l] is the unscaled
-    d C_l / d flow that of_census_bwd_multi scales into d(flow), or None without want_grad."""
+    d C_l / d flow that of_census_bwd_multi scales into d(flow), or None without want_grad.
+    ``wts``: per-level pixel weights (of_census_fwd_multi_w), None for the unweighted call."""
     lib = _lib.lib()
     ns = len(fl)
     n = fl[0].shape[0]
@@ -2430,12 +2436,17 @@ def _census_fwd(pyr, fl, radius, coefs, want_grad, wc=0):
     planes = [torch.empty_like(f) for f in fl] if want_grad else None
     wsf = [lib.of_census_workspace_floats(n, h, w) for h, w in zip(hs, ws_)]
     wss = [torch.empty(k, device=fl[0].device) if k > 0 else None for k in wsf]
+    wsp = _opt_ptrs(wss) if any(wsf) else None
+    plp = _arr(C.c_void_p, [p.data_ptr() for p in planes]) if planes is not None else None
+    if wts is not None:
+        call("of_census_fwd_multi_w", _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
+             _arr(C.c_void_p, [f.data_ptr() for f in fl]), _opt_ptrs(wts), n,
+             _arr(C.c_int, hs), _arr(C.c_int, ws_), ns, radius, _arr(C.c_float, coefs), wsp, plp,
+             _ptr(parts), wc, _stream())
+        return parts, planes
     _call_cv("of_census_fwd_multi", wc, _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
              _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs),
-             _arr(C.c_int, ws_), ns, radius, _arr(C.c_float, coefs),
-             _arr(C.c_void_p, [t.data_ptr() if t is not None else None for t in wss])
-             if any(wsf) else None,
-             _arr(C.c_void_p, [p.data_ptr() for p in planes]) if planes is not None else None,
+             _arr(C.c_int, ws_), ns, radius, _arr(C.c_float, coefs), wsp, plp,
              _ptr(parts), _stream())
     return parts, planes
 
@@ -2508,11 +2519,14 @@ class _CensusFlowLoss(torch.autograd.Function):
     """photometric_weight * photometric + census_weight * census + smoothness_weight *
     smoothness on one image pyramid; a term whose weight is 0 launches nothing.  One Function
     for all terms because of the FlowGrad protocol (see _FlowLoss): in the backward the first
-    term present overwrites each level's d(flow) output and the later ones add into it."""
+    term present overwrites each level's d(flow) output and the later ones add into it.
+    ``cfg`` may end with per-level pixel weights of the two data terms ((n,h,w) tensors,
+    constants: occlusion masks), which route them to the ``_w`` kernels; the smoothness term
+    is not weighted."""
 
     @staticmethod
     def forward(ctx, batch_imgs, fgs, cfg, *flows):
-        pw, cw, radius, sw, edge_alpha, eps, wc = cfg
+        pw, cw, radius, sw, edge_alpha, eps, wc, wts = cfg
         _check_dev(batch_imgs, *flows)
         ctx.wc = wc
         assert pw != 0 or cw != 0, "a data term is needed: both data weights are 0"
@@ -2535,9 +2549,15 @@ class _CensusFlowLoss(torch.autograd.Function):
         if pw != 0:
             nparts = [_lib.lib().of_photo_l1_partials(n, h, w) for h, w in zip(hs, ws_)]
             parts = torch.empty(sum(nparts), device=b.device)
-            _call_cv("of_photo_l1_fwd_multi", wc, _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
-                     _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs),
-                     _arr(C.c_int, ws_), ns, _ptr(parts), s)
+            if wts is not None:
+                call("of_photo_l1_fwd_multi_w", _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
+                     _arr(C.c_void_p, [f.data_ptr() for f in fl]), _opt_ptrs(wts), n,
+                     _arr(C.c_int, hs), _arr(C.c_int, ws_), ns, _ptr(parts), wc, s)
+            else:
+                _call_cv("of_photo_l1_fwd_multi", wc,
+                         _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
+                         _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs),
+                         _arr(C.c_int, ws_), ns, _ptr(parts), s)
             off = 0
             for k in range(ns):
                 groups.append((parts.data_ptr() + 4 * off, nparts[k], coefs[k]))
@@ -2548,7 +2568,7 @@ class _CensusFlowLoss(torch.autograd.Function):
         planes = None
         if cw != 0:
             cparts, planes = _census_fwd(pyr, fl, radius, ccoefs, any(ctx.needs_input_grad[3:]),
-                                         wc)
+                                         wc, wts)
             groups.append((cparts.data_ptr(), cparts.numel(), 1.0))
             keep.append(cparts)
         cv, ch = _smooth_coefs(n, hs, ws_, sw)
@@ -2561,6 +2581,7 @@ class _CensusFlowLoss(torch.autograd.Function):
              _arr(C.c_int, [g[1] for g in groups]), _arr(C.c_float, [g[2] for g in groups]),
              len(groups), _ptr(loss), s)
         ctx.save_for_backward(*pyr, *fl, *(planes or []))
+        ctx.wts = wts if pw != 0 else None      # the photometric backward reads them again
         ctx.cfg = (ns, pw, cw, sw, edge_alpha, eps, coefs, ccoefs, cv, ch)
         return loss
 
@@ -2590,7 +2611,18 @@ class _CensusFlowLoss(torch.autograd.Function):
             m = len(lv)
             n = pyr[0].shape[0]
             written = 0                # the first term present writes, the others add
-            if pw != 0:
+            if pw != 0 and ctx.wts is not None:
+                call("of_photo_l1_bwd_multi_w",
+                     _arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]),
+                     _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]),
+                     _opt_ptrs([ctx.wts[k] for k, _, _ in lv]), n,
+                     _arr(C.c_int, [pyr[k].shape[1] for k, _, _ in lv]),
+                     _arr(C.c_int, [pyr[k].shape[2] for k, _, _ in lv]), m,
+                     _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
+                     _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
+                     _arr(C.c_int, [ld for _, _, ld in lv]), ctx.wc, s)
+                written = 1
+            elif pw != 0:
                 _call_cv("of_photo_l1_bwd_multi", ctx.wc,
                          _arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]),
                          _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]), n,
@@ -2608,15 +2640,82 @@ class _CensusFlowLoss(torch.autograd.Function):
         return (None, None, None, *grads)
 
 
+def _pixel_weights(weights, flows):
+    """census_flow_loss's ``weights`` as contiguous fp32 (n,h,w) tensors (None entries stay:
+    weight 1 for that level)."""
+    if len(weights) != len(flows):
+        raise ValueError("weights: %d levels for %d flows" % (len(weights), len(flows)))
+    out = []
+    for k, (wt, f) in enumerate(zip(weights, flows)):
+        if wt is not None:
+            if tuple(wt.shape) != tuple(f.shape[:3]):
+                raise ValueError("weights[%d] has shape %s, expected %s"
+                                 % (k, tuple(wt.shape), tuple(f.shape[:3])))
+            _check_dev(f, wt)
+            wt = wt.detach().contiguous()
+        out.append(wt)
+    return out
+
+
 def census_flow_loss(batch_imgs, flows, census_weight, census_radius=3, photometric_weight=1.0,
-                     smoothness_weight=0.0, edge_alpha=0.0, eps=1e-4, convention="reference"):
+                     smoothness_weight=0.0, edge_alpha=0.0, eps=1e-4, convention="reference",
+                     weights=None):
     """The training loss with the census data term: ``photometric_weight`` times
     photometric_loss plus ``census_weight`` times census_loss plus ``smoothness_weight`` times
     flow_smoothness, in one Function (see _CensusFlowLoss).  At least one data weight must be
-    non-zero; the kernels of a term whose weight is 0 are not launched."""
+    non-zero; the kernels of a term whose weight is 0 are not launched.
+
+    ``weights``: per level a (n,h,w) tensor of non-negative pixel weights for the two data
+    terms (occlusion_masks' output, or None for a level of weight 1).  They are constants; a
+    pixel's photometric error and its census window sum are multiplied by its weight, the
+    normalisers stay the means over all pixels, and the smoothness term is not weighted."""
     fgs = [getattr(f, "_of_flowgrad", None) for f in flows]
     if any(fg is not None and fg.shape != tuple(f.shape) for fg, f in zip(fgs, flows)):
         fgs = [None] * len(flows)
+    wts = _pixel_weights(weights, flows) if weights is not None else None
     cfg = (float(photometric_weight), float(census_weight), _census_radius(census_radius),
-           float(smoothness_weight), float(edge_alpha), float(eps), warp_convention(convention))
+           float(smoothness_weight), float(edge_alpha), float(eps), warp_convention(convention),
+           wts)
     return _CensusFlowLoss.apply(batch_imgs, fgs, cfg, *flows)
+
+
+# ============================================================== occlusion masks =====
+OCCLUSION_MODES = {"border": _lib.OCC_BORDER, "fb": _lib.OCC_FB}
+
+
+def occlusion_masks(flows, mode, alpha1=0.01, alpha2=0.5, convention="image"):
+    """Per level a (n,h,w) float mask, 1.0 where the data terms may score the pixel and 0.0
+    where its correspondent is out of frame or hidden (include/oflow.h, of_occ_mask_multi;
+    DESIGN.md "Occlusion masks").  No autograd: the masks are constants.
+
+    ``mode`` "border": 1 iff the sample point (j + f0, i + f1) lies inside the frame.
+    ``mode`` "fb": the batch is [forward flows ; flows of the same pairs swapped] (n even,
+    pair_stride = n // 2); 1 iff inside the frame and |f + g~|^2 <= alpha1 (|f|^2 + |g~|^2) +
+    alpha2_s, g~ the partner's flow sampled at the sample point.  ``alpha2`` is in squared
+    full-resolution pixels: level s (1/2^(s+1) of the resolution, flows in its own pixels)
+    gets alpha2 / 4^(s+1).  Image convention only: a reference-convention flow is not a
+    displacement."""
+    if mode not in OCCLUSION_MODES:
+        raise ValueError("occlusion mode must be one of %s, got %r"
+                         % (sorted(OCCLUSION_MODES), mode))
+    if warp_convention(convention) != _lib.WARP_IMAGE:
+        raise ValueError("occlusion masks need the image warp convention: a %r-convention flow "
+                         "is not a displacement" % (convention,))
+    if not alpha1 >= 0 or not alpha2 >= 0:
+        raise ValueError("occlusion alphas must be >= 0, got %r and %r" % (alpha1, alpha2))
+    ns = len(flows)
+    if not 1 <= ns <= 8:
+        raise ValueError("occlusion_masks takes 1..8 levels, got %d" % ns)
+    n = flows[0].shape[0]
+    if mode == "fb" and (n < 2 or n % 2):
+        raise ValueError("occlusion mode 'fb' needs the doubled batch [forward ; swapped]: "
+                         "an even number of images, got %d" % n)
+    _check_dev(*flows)
+    fl = [f.detach().contiguous() for f in flows]
+    masks = [torch.empty(f.shape[:3], device=f.device) for f in fl]
+    call("of_occ_mask_multi", _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, n // 2,
+         _arr(C.c_int, [f.shape[1] for f in fl]), _arr(C.c_int, [f.shape[2] for f in fl]), ns,
+         OCCLUSION_MODES[mode], float(alpha1),
+         _arr(C.c_float, [float(alpha2) / 4.0 ** (s + 1) for s in range(ns)]),
+         _arr(C.c_void_p, [m.data_ptr() for m in masks]), _stream())
+    return masks

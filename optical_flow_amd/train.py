@@ -216,6 +216,13 @@ class Trainer:
         store.zero_grad()
         if self.reducer is not None:
             self.reducer.begin()
+        nb = batch_imgs.shape[0]
+        if getattr(self.loss_layer, "occlusion", "none") == "fb":
+            # forward-backward check: the net also sees every pair with its images exchanged
+            # ([batch ; swapped], device-only ops: the step still captures); the loss is the
+            # mean over both directions
+            batch_imgs = torch.cat([batch_imgs,
+                                    torch.cat([batch_imgs[..., 3:], batch_imgs[..., :3]], -1)], 0)
         flows = self.flow_net(batch_imgs)
         loss_value = self.loss_layer(batch_imgs, flows)
         loss_value.backward()
@@ -226,7 +233,8 @@ class Trainer:
             bufs = store.buffers if getattr(self.flow_net, "bn_mode", "") == "training" else None
             scale = self.reducer.finish(buffers=bufs)
         self.optimizer.apply_gradients(grad_scale=scale)
-        return loss_value.detach(), [f.detach() for f in flows]
+        # "fb": the caller sees the forward flows of the batch it passed
+        return loss_value.detach(), [f.detach()[:nb] for f in flows]
 
     def graphed(self, batch_imgs, warmup: int = 2, capture_ctx=None):
         """The step captured once as a HIP graph over a static input batch (train.py:47-48
@@ -400,6 +408,15 @@ def build_parser():
     ap.add_argument("--warp-convention", default="reference", choices=("reference", "image"),
                     help="the grid every warp adds the flow to: the reference's transposed grid "
                          "(default) or image coordinates (flow = (x, y) displacement)")
+    ap.add_argument("--occlusion", default="none", choices=("none", "border", "fb"),
+                    help="mask the data terms where the sample leaves the frame (border) or "
+                         "also fails the forward-backward check (fb: every step runs the "
+                         "pairs both ways); needs --warp-convention image")
+    ap.add_argument("--occ-alpha1", type=float, default=0.01,
+                    help="relative tolerance of the forward-backward check")
+    ap.add_argument("--occ-alpha2", type=float, default=0.5,
+                    help="absolute tolerance of the forward-backward check, in squared "
+                         "full-resolution pixels")
     ap.add_argument("--eval-kitti-flow", default=None, metavar="ROOT",
                     help="KITTI 2015 flow root: EPE and Fl-all against its ground truth after "
                          "every --eval-every epochs and at the end (needs --warp-convention image)")
@@ -442,6 +459,19 @@ def check_eval_args(args):
         raise ValueError("--eval-every must be >= 1, got %d" % args.eval_every)
 
 
+def check_occlusion_args(args):
+    """--occlusion masks are defined on image displacements, so anything but "none" needs
+    --warp-convention image; the alphas are >= 0.  ValueError otherwise (main turns it into a
+    parser error)."""
+    if args.occ_alpha1 < 0 or args.occ_alpha2 < 0:
+        raise ValueError("--occ-alpha1 and --occ-alpha2 must be >= 0, got %r and %r"
+                         % (args.occ_alpha1, args.occ_alpha2))
+    if args.occlusion != "none" and args.warp_convention != "image":
+        raise ValueError("--occlusion %s needs --warp-convention image: a reference-convention "
+                         "flow is not a displacement, where the pixel went has no meaning"
+                         % args.occlusion)
+
+
 def header_record(args, augment=None):
     """The step log's header record (no "step" key) for a run with any non-default loss,
     augmentation, clipping or warp-convention option; None for a default run, whose log holds
@@ -450,8 +480,9 @@ def header_record(args, augment=None):
               args.photometric_weight != 1.0)
     clip = args.clip_norm is not None or args.skip_nonfinite or args.log_grad_norm
     image = args.warp_convention == "image"
+    occ = (args.occlusion != "none" or args.occ_alpha1 != 0.01 or args.occ_alpha2 != 0.5)
     if not (args.smoothness_weight or args.edge_alpha or augment is not None or census or clip
-            or image):
+            or image or occ):
         return None
     head = {"header": True, "smoothness_weight": args.smoothness_weight,
             "edge_alpha": args.edge_alpha}
@@ -465,6 +496,9 @@ def header_record(args, augment=None):
                     log_grad_norm=args.log_grad_norm)
     if image:
         head["warp_convention"] = args.warp_convention
+    if occ:
+        head.update(occlusion=args.occlusion, occ_alpha1=args.occ_alpha1,
+                    occ_alpha2=args.occ_alpha2)
     if args.eval_kitti_flow is not None:
         head.update(eval_kitti_flow=args.eval_kitti_flow, eval_every=args.eval_every)
     return head
@@ -483,6 +517,7 @@ def main(argv=None):
 
     try:
         check_eval_args(args)
+        check_occlusion_args(args)
     except ValueError as e:
         ap.error(str(e))
 
@@ -491,7 +526,9 @@ def main(argv=None):
                                census_weight=args.census_weight,
                                census_radius=args.census_radius,
                                photometric_weight=args.photometric_weight,
-                               warp_convention=args.warp_convention)
+                               warp_convention=args.warp_convention,
+                               occlusion=args.occlusion, occlusion_alpha1=args.occ_alpha1,
+                               occlusion_alpha2=args.occ_alpha2)
     except ValueError as e:
         ap.error(str(e))
     try:
