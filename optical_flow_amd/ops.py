@@ -8,7 +8,7 @@ from __future__ import annotations
 import contextlib
 import os
 import ctypes as C
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -2111,106 +2111,22 @@ def halves(x):
 
 
 # ================================================================ photometric loss =====
-class _PhotoLoss(torch.autograd.Function):
-    """LossLayer.__call__ (loss.py:5-32): mean over scales of mean |img1_s - warp(img2_s)|.
-    The image pyramid (tf.image.resize) is built by one kernel per level; the warp, the
-    difference, |.| and the reduction are fused per scale; the backward writes d(flow) per
-    scale directly (the images are constants)."""
-
-    @staticmethod
-    def forward(ctx, batch_imgs, fgs_wc, *flows):
-        fgs, wc = fgs_wc                 # (FlowGrad per level, warp convention code)
-        _check_dev(batch_imgs, *flows)
-        ctx.fgs = fgs
-        ctx.wc = wc
-        b = batch_imgs.contiguous()
-        n, H, W, c = b.shape
-        assert c == 6
-        ns = len(flows)
-        s = _stream()
-        pyr = []
-        for k in range(ns):
-            h = int(H / (2.0 ** (k + 1)))
-            w = int(W / (2.0 ** (k + 1)))
-            assert flows[k].shape[1] == h and flows[k].shape[2] == w, \
-                "flow %d has shape %s, expected (B,%d,%d,2)" % (k, tuple(flows[k].shape), h, w)
-            pyr.append(torch.empty((n, h, w, 6), device=b.device))
-        # every level is a resize of the full-resolution batch (loss.py:17-18)
-        outs = (C.c_void_p * ns)(*[p.data_ptr() for p in pyr])
-        call("of_pyramid6", _ptr(b), n, H, W, ns, outs, s)
-        # every scale's partial sums in one launch (of_photo_l1_fwd_multi), one partial array
-        fl = [f.contiguous() for f in flows]
-        hs = [p.shape[1] for p in pyr]
-        ws_ = [p.shape[2] for p in pyr]
-        nparts = [_lib.lib().of_photo_l1_partials(n, h, w) for h, w in zip(hs, ws_)]
-        coefs = [1.0 / (ns * n * h * w * 3) for h, w in zip(hs, ws_)]
-        parts = torch.empty(sum(nparts), device=b.device)
-        _call_cv("of_photo_l1_fwd_multi", wc, (C.c_void_p * ns)(*[p.data_ptr() for p in pyr]),
-                 (C.c_void_p * ns)(*[f.data_ptr() for f in fl]), n, (C.c_int * ns)(*hs),
-                 (C.c_int * ns)(*ws_), ns, _ptr(parts), s)
-        offs = [0]
-        for k in range(ns):
-            offs.append(offs[-1] + nparts[k])
-        loss = torch.empty((), device=b.device)
-        call("of_sum_partials",
-             (C.c_void_p * ns)(*[parts.data_ptr() + 4 * offs[k] for k in range(ns)]),
-             (C.c_int * ns)(*nparts), (C.c_float * ns)(*coefs), ns, _ptr(loss), s)
-        ctx.save_for_backward(*pyr, *fl)
-        ctx.ns = ns
-        ctx.coefs = coefs
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        ns = ctx.ns
-        saved = ctx.saved_tensors
-        pyr, flows = saved[:ns], saved[ns:]
-        dloss = dloss.contiguous()
-        s = _stream()
-        grads, lv = [], []          # lv: (level, output, row stride) of one multi launch
-        for k in range(ns):
-            if not ctx.needs_input_grad[2 + k]:
-                grads.append(None)
-                continue
-            fg = ctx.fgs[k]
-            if fg is not None:         # into the flow head's padded gradient (FlowGrad)
-                buf = fg.buffer()
-                fg.filled = True
-                grads.append(buf[..., :2])
-                lv.append((k, buf, 4))
-                continue
-            df = torch.empty_like(flows[k])
-            grads.append(df)
-            lv.append((k, df, 2))
-        if lv:
-            m = len(lv)
-            n = pyr[0].shape[0]
-            _call_cv("of_photo_l1_bwd_multi", ctx.wc,
-                     (C.c_void_p * m)(*[pyr[k].data_ptr() for k, _, _ in lv]),
-                     (C.c_void_p * m)(*[flows[k].data_ptr() for k, _, _ in lv]), n,
-                     (C.c_int * m)(*[pyr[k].shape[1] for k, _, _ in lv]),
-                     (C.c_int * m)(*[pyr[k].shape[2] for k, _, _ in lv]), m,
-                     (C.c_float * m)(*[ctx.coefs[k] for k, _, _ in lv]), _ptr(dloss),
-                     (C.c_void_p * m)(*[o.data_ptr() for _, o, _ in lv]),
-                     (C.c_int * m)(*[ld for _, _, ld in lv]), s)
-        return (None, None, *grads)
-
-
-def photometric_loss(batch_imgs, flows, convention="reference"):
-    fgs = [getattr(f, "_of_flowgrad", None) for f in flows]
-    if any(fg is not None and fg.shape != tuple(f.shape) for fg, f in zip(fgs, flows)):
-        fgs = [None] * len(flows)
-    return _PhotoLoss.apply(batch_imgs, (fgs, warp_convention(convention)), *flows)
-
-
-# ============================================================== flow smoothness =====
+# The training loss: photometric, census and smoothness terms over one image pyramid, in one
+# autograd Function (_Loss, below).  Each term has a forward and a backward helper of the same
+# shape; ``lv`` is the list of (level, output, row stride) that _grad_targets builds.
 def _arr(ctype, vals):
     return (ctype * len(vals))(*vals)
 
 
+def _opt_ptrs(ts):
+    """A pointer array over tensors; None entries become NULL."""
+    return _arr(C.c_void_p, [t.data_ptr() if t is not None else None for t in ts])
+
+
 def _pyramid6(b, flows):
     """The loss's image pyramid (loss.py:17-18): level k is batch_imgs resized to
-    H/2^(k+1) x W/2^(k+1), which must be flows[k]'s size."""
+    H/2^(k+1) x W/2^(k+1), which must be flows[k]'s size.  Every level is a resize of the
+    full-resolution batch, all of them in one launch."""
     n, H, W, c = b.shape
     assert c == 6
     pyr = []
@@ -2225,6 +2141,51 @@ def _pyramid6(b, flows):
     return pyr
 
 
+# Which C entry serves a data term: the plain name in the reference convention without pixel
+# weights (the call it always was), its ``_cv`` form in the image convention (_call_cv), its
+# ``_w`` form, which takes both the weights and the convention, when weights are given.
+def _photo_fwd(pyr, fl, wts, wc):
+    """of_photo_l1_fwd_multi over every level (LossLayer.__call__, loss.py:5-32: the warp, the
+    difference, |.| and the reduction fused per scale): (partials, per-level counts).  Level
+    l's slice sums to its unscaled sum of |img1 - warp(img2)|; the caller's sum applies the
+    coefficients.  ``wts``: per-level pixel weights, None for the unweighted call."""
+    ns = len(fl)
+    n = fl[0].shape[0]
+    hs = [p.shape[1] for p in pyr]
+    ws_ = [p.shape[2] for p in pyr]
+    nparts = [_lib.lib().of_photo_l1_partials(n, h, w) for h, w in zip(hs, ws_)]
+    parts = torch.empty(sum(nparts), device=fl[0].device)
+    imgs = _arr(C.c_void_p, [p.data_ptr() for p in pyr])
+    fls = _arr(C.c_void_p, [f.data_ptr() for f in fl])
+    if wts is not None:
+        call("of_photo_l1_fwd_multi_w", imgs, fls, _opt_ptrs(wts), n, _arr(C.c_int, hs),
+             _arr(C.c_int, ws_), ns, _ptr(parts), wc, _stream())
+    else:
+        _call_cv("of_photo_l1_fwd_multi", wc, imgs, fls, n, _arr(C.c_int, hs),
+                 _arr(C.c_int, ws_), ns, _ptr(parts), _stream())
+    return parts, nparts
+
+
+def _photo_bwd(pyr, flows, wts, lv, coefs, dloss, wc):
+    """of_photo_l1_bwd_multi for the levels in ``lv``: writes (never adds) each level's
+    d(flow); the images are constants."""
+    m = len(lv)
+    n = pyr[0].shape[0]
+    imgs = _arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv])
+    fls = _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv])
+    tail = (_arr(C.c_int, [pyr[k].shape[1] for k, _, _ in lv]),
+            _arr(C.c_int, [pyr[k].shape[2] for k, _, _ in lv]), m,
+            _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
+            _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
+            _arr(C.c_int, [ld for _, _, ld in lv]))
+    if wts is not None:
+        call("of_photo_l1_bwd_multi_w", imgs, fls, _opt_ptrs([wts[k] for k, _, _ in lv]), n,
+             *tail, wc, _stream())
+    else:
+        _call_cv("of_photo_l1_bwd_multi", wc, imgs, fls, n, *tail, _stream())
+
+
+# ============================================================== flow smoothness =====
 def _smooth_coefs(n, hs, ws, scale):
     """The normalisers of the smoothness term, times ``scale``: the mean over each
     direction's pairs and over the levels; a direction with no pairs contributes 0."""
@@ -2235,8 +2196,11 @@ def _smooth_coefs(n, hs, ws, scale):
 
 
 def _smooth_fwd(pyr, fl, edge_alpha, eps, cv, ch):
-    """of_flow_smooth_fwd_multi over every level: the partials (they sum to the weighted
-    term, the coefficients are applied in the kernel)."""
+    """of_flow_smooth_fwd_multi over every level (include/oflow.h): the mean Charbonnier
+    penalty of the vertical plus that of the horizontal first differences of the flow, each
+    weighted by exp(-edge_alpha * mean|d image1|) across the same pair.  Returns the partials
+    (they sum to the weighted term, the coefficients are applied in the kernel).  The images
+    are only read when ``edge_alpha`` is not 0."""
     ns = len(fl)
     n = fl[0].shape[0]
     hs = [f.shape[1] for f in fl]
@@ -2251,8 +2215,7 @@ def _smooth_fwd(pyr, fl, edge_alpha, eps, cv, ch):
 
 
 def _smooth_bwd(pyr, flows, lv, edge_alpha, eps, cv, ch, dloss, accumulate):
-    """of_flow_smooth_bwd_multi for the levels in ``lv`` ((level, output, row stride), as
-    _PhotoLoss.backward builds them)."""
+    """of_flow_smooth_bwd_multi for the levels in ``lv``."""
     m = len(lv)
     n = flows[0].shape[0]
     imgs = (_arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]) if edge_alpha != 0
@@ -2266,148 +2229,6 @@ def _smooth_bwd(pyr, flows, lv, edge_alpha, eps, cv, ch, dloss, accumulate):
          _arr(C.c_int, [ld for _, _, ld in lv]), accumulate, _stream())
 
 
-class _FlowSmooth(torch.autograd.Function):
-    """Edge-aware first-order smoothness of every level's flow (include/oflow.h,
-    of_flow_smooth_fwd_multi): mean over levels of the mean Charbonnier penalty of the
-    vertical plus that of the horizontal first differences, each weighted by
-    exp(-edge_alpha * mean|d image1|) across the same pair.  The images are constants."""
-
-    @staticmethod
-    def forward(ctx, batch_imgs, cfg, *flows):
-        edge_alpha, eps = cfg
-        _check_dev(batch_imgs, *flows)
-        assert 1 <= len(flows) <= 8
-        fl = [f.contiguous() for f in flows]
-        n = fl[0].shape[0]
-        pyr = _pyramid6(batch_imgs.contiguous(), fl) if edge_alpha != 0 else []
-        cv, ch = _smooth_coefs(n, [f.shape[1] for f in fl], [f.shape[2] for f in fl], 1.0)
-        parts = _smooth_fwd(pyr, fl, edge_alpha, eps, cv, ch)
-        out = torch.empty((), device=parts.device)
-        call("of_sum_partials", _arr(C.c_void_p, [parts.data_ptr()]),
-             _arr(C.c_int, [parts.numel()]), _arr(C.c_float, [1.0]), 1, _ptr(out), _stream())
-        ctx.save_for_backward(*pyr, *fl)
-        ctx.cfg = (len(fl), edge_alpha, eps, cv, ch)
-        return out
-
-    @staticmethod
-    def backward(ctx, dloss):
-        ns, edge_alpha, eps, cv, ch = ctx.cfg
-        saved = ctx.saved_tensors
-        pyr, flows = saved[:len(saved) - ns], saved[len(saved) - ns:]
-        dloss = dloss.contiguous()
-        grads, lv = [], []
-        for k in range(ns):
-            if not ctx.needs_input_grad[2 + k]:
-                grads.append(None)
-                continue
-            df = torch.empty_like(flows[k])
-            grads.append(df)
-            lv.append((k, df, 2))
-        if lv:
-            _smooth_bwd(pyr, flows, lv, edge_alpha, eps, cv, ch, dloss, 0)
-        return (None, None, *grads)
-
-
-def flow_smoothness(batch_imgs, flows, edge_alpha=0.0, eps=1e-4):
-    """The smoothness term alone (a scalar; plain gradients for the flows).  The image
-    pyramid is only built when ``edge_alpha`` is not 0."""
-    return _FlowSmooth.apply(batch_imgs, (float(edge_alpha), float(eps)), *flows)
-
-
-class _FlowLoss(torch.autograd.Function):
-    """photometric + smoothness_weight * smoothness, the training loss with the regulariser
-    on: what _PhotoLoss does, then the smoothness forward on the same pyramid tensors.  One
-    Function for both terms because of the FlowGrad protocol: the loss writes a flow's
-    gradient buffer once (of_photo_l1_bwd_multi overwrites, of_flow_smooth_bwd_multi then adds
-    into the same outputs) and upscale_flow's backward adds to it afterwards."""
-
-    @staticmethod
-    def forward(ctx, batch_imgs, fgs, cfg, *flows):
-        weight, edge_alpha, eps, wc = cfg
-        _check_dev(batch_imgs, *flows)
-        ctx.fgs = fgs
-        b = batch_imgs.contiguous()
-        n = b.shape[0]
-        ns = len(flows)
-        assert 1 <= ns <= 7, "of_sum_partials takes 8 groups: 7 levels and the smoothness term"
-        s = _stream()
-        fl = [f.contiguous() for f in flows]
-        pyr = _pyramid6(b, fl)
-        hs = [p.shape[1] for p in pyr]
-        ws_ = [p.shape[2] for p in pyr]
-        nparts = [_lib.lib().of_photo_l1_partials(n, h, w) for h, w in zip(hs, ws_)]
-        coefs = [1.0 / (ns * n * h * w * 3) for h, w in zip(hs, ws_)]
-        parts = torch.empty(sum(nparts), device=b.device)
-        _call_cv("of_photo_l1_fwd_multi", wc, _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
-                 _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs),
-                 _arr(C.c_int, ws_), ns, _ptr(parts), s)
-        cv, ch = _smooth_coefs(n, hs, ws_, weight)
-        sparts = _smooth_fwd(pyr, fl, edge_alpha, eps, cv, ch)
-        offs = [0]
-        for k in range(ns):
-            offs.append(offs[-1] + nparts[k])
-        # the smoothness partials carry their coefficients: one more group, coefficient 1
-        groups = [(parts.data_ptr() + 4 * offs[k], nparts[k], coefs[k]) for k in range(ns)]
-        groups.append((sparts.data_ptr(), sparts.numel(), 1.0))
-        loss = torch.empty((), device=b.device)
-        call("of_sum_partials", _arr(C.c_void_p, [g[0] for g in groups]),
-             _arr(C.c_int, [g[1] for g in groups]), _arr(C.c_float, [g[2] for g in groups]),
-             len(groups), _ptr(loss), s)
-        ctx.save_for_backward(*pyr, *fl)
-        ctx.cfg = (ns, edge_alpha, eps, coefs, cv, ch)
-        ctx.wc = wc
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        ns, edge_alpha, eps, coefs, cv, ch = ctx.cfg
-        saved = ctx.saved_tensors
-        pyr, flows = saved[:ns], saved[ns:]
-        dloss = dloss.contiguous()
-        s = _stream()
-        grads, lv = [], []          # lv: (level, output, row stride) of one multi launch
-        for k in range(ns):
-            if not ctx.needs_input_grad[3 + k]:
-                grads.append(None)
-                continue
-            fg = ctx.fgs[k]
-            if fg is not None:         # into the flow head's padded gradient (FlowGrad)
-                buf = fg.buffer()
-                fg.filled = True
-                grads.append(buf[..., :2])
-                lv.append((k, buf, 4))
-                continue
-            df = torch.empty_like(flows[k])
-            grads.append(df)
-            lv.append((k, df, 2))
-        if lv:
-            m = len(lv)
-            n = pyr[0].shape[0]
-            # the photometric gradient writes every output, the smoothness gradient adds
-            _call_cv("of_photo_l1_bwd_multi", ctx.wc,
-                     _arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]),
-                     _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]), n,
-                     _arr(C.c_int, [pyr[k].shape[1] for k, _, _ in lv]),
-                     _arr(C.c_int, [pyr[k].shape[2] for k, _, _ in lv]), m,
-                     _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
-                     _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
-                     _arr(C.c_int, [ld for _, _, ld in lv]), s)
-            _smooth_bwd(pyr, flows, lv, edge_alpha, eps, cv, ch, dloss, 1)
-        return (None, None, None, *grads)
-
-
-def flow_loss(batch_imgs, flows, smoothness_weight, edge_alpha=0.0, eps=1e-4,
-              convention="reference"):
-    """The training loss with the smoothness regulariser: photometric_loss plus
-    ``smoothness_weight`` times flow_smoothness, in one Function (see _FlowLoss)."""
-    fgs = [getattr(f, "_of_flowgrad", None) for f in flows]
-    if any(fg is not None and fg.shape != tuple(f.shape) for fg, f in zip(fgs, flows)):
-        fgs = [None] * len(flows)
-    return _FlowLoss.apply(batch_imgs, fgs,
-                           (float(smoothness_weight), float(edge_alpha), float(eps),
-                            warp_convention(convention)), *flows)
-
-
 # ================================================================== census term =====
 def _census_coefs(n, hs, ws, scale):
     """The normalisers of the census term, times ``scale``: the mean over each level's
@@ -2416,15 +2237,11 @@ def _census_coefs(n, hs, ws, scale):
     return [scale / (ns * n * h * w) for h, w in zip(hs, ws)]
 
 
-def _opt_ptrs(ts):
-    """A pointer array over tensors; None entries become NULL."""
-    return _arr(C.c_void_p, [t.data_ptr() if t is not None else None for t in ts])
-
-
 def _census_fwd(pyr, fl, radius, coefs, want_grad, wc=0, wts=None):
-    """of_census_fwd_multi over every level: (partials, planes).  The partials sum to the
-    weighted term (the coefficients are applied in the kernel); planes[l] is the unscaled
-    d C_l / d flow that of_census_bwd_multi scales into d(flow), or None without want_grad.
+    """of_census_fwd_multi over every level (the soft ternary census term, include/oflow.h):
+    (partials, planes).  The partials sum to the weighted term (the coefficients are applied
+    in the kernel); planes[l] is the unscaled d C_l / d flow (the window loop forms both) that
+    of_census_bwd_multi scales into d(flow), or None without want_grad.
     ``wts``: per-level pixel weights (of_census_fwd_multi_w), None for the unweighted call."""
     lib = _lib.lib()
     ns = len(fl)
@@ -2452,8 +2269,7 @@ def _census_fwd(pyr, fl, radius, coefs, want_grad, wc=0, wts=None):
 
 
 def _census_bwd(planes, lv, coefs, dloss, accumulate):
-    """of_census_bwd_multi for the levels in ``lv`` ((level, output, row stride), as
-    _PhotoLoss.backward builds them)."""
+    """of_census_bwd_multi for the levels in ``lv``."""
     m = len(lv)
     n = planes[0].shape[0]
     call("of_census_bwd_multi", _arr(C.c_void_p, [planes[k].data_ptr() for k, _, _ in lv]), n,
@@ -2464,43 +2280,168 @@ def _census_bwd(planes, lv, coefs, dloss, accumulate):
          _arr(C.c_int, [ld for _, _, ld in lv]), accumulate, _stream())
 
 
-class _Census(torch.autograd.Function):
-    """The soft ternary census term of every level (include/oflow.h, of_census_fwd_multi):
-    mean over levels of C_l / (B h_l w_l).  The forward also leaves d C_l / d flow (the window
-    loop forms both); the backward scales it.  The images are constants."""
+# ============================================================ the loss Function =====
+def _flowgrads(flows):
+    """Each flow's FlowGrad (None where a flow has none); if any of them does not have its
+    flow's shape, none is used."""
+    fgs = [getattr(f, "_of_flowgrad", None) for f in flows]
+    if any(fg is not None and fg.shape != tuple(f.shape) for fg, f in zip(fgs, flows)):
+        fgs = [None] * len(flows)
+    return fgs
+
+
+def _grad_targets(fgs, like, needs):
+    """Where a backward writes each level's d(flow): (grads, lv).  ``grads`` is what autograd
+    gets back per flow (None where ``needs`` says no gradient is wanted), ``lv`` the (level,
+    output, row stride) of one multi launch.  A level with a FlowGrad is written into the flow
+    head's padded gradient at row stride 4 and autograd gets the view of its first two
+    channels; any other level gets a fresh tensor shaped like ``like[k]``, row stride 2."""
+    grads, lv = [], []
+    for k, need in enumerate(needs):
+        if not need:
+            grads.append(None)
+            continue
+        fg = fgs[k] if fgs is not None else None
+        if fg is not None:
+            buf = fg.buffer()
+            fg.filled = True
+            grads.append(buf[..., :2])
+            lv.append((k, buf, 4))
+            continue
+        df = torch.empty_like(like[k])
+        grads.append(df)
+        lv.append((k, df, 2))
+    return grads, lv
+
+
+class _LossCfg(NamedTuple):
+    pw: float = 0.0                 # weights of the photometric, census and smoothness terms
+    cw: float = 0.0
+    sw: float = 0.0
+    radius: int = 3                 # census window radius
+    edge_alpha: float = 0.0         # smoothness: edge weighting and the Charbonnier eps
+    eps: float = 1e-4
+    wc: int = _lib.WARP_REFERENCE   # warp convention code of the data terms
+    wts: Optional[list] = None      # per-level pixel weights of the data terms ((n,h,w)
+    #                                 tensors, constants: occlusion masks); None: unweighted
+    fgs: Optional[list] = None      # per-level FlowGrad (_flowgrads); None: plain gradients
+
+
+class _Loss(torch.autograd.Function):
+    """pw * photometric + cw * census + sw * smoothness, each the mean over the levels of
+    that level's mean, on one image pyramid; the images are constants.  A term whose weight
+    is 0 launches nothing, and the pyramid is only built when a term reads it (a data term,
+    or the smoothness term with edge_alpha != 0).  The smoothness term is never weighted by
+    ``wts``.
+
+    One Function for all terms because of the FlowGrad protocol: the loss writes a flow's
+    gradient buffer once and upscale_flow's backward adds to it afterwards, so two Functions
+    returning gradients for the same flow would break it.  In the backward the terms run
+    photometric, census, smoothness; the first one present overwrites each level's d(flow)
+    output and the later ones add into it (``accumulate = 1``)."""
 
     @staticmethod
-    def forward(ctx, batch_imgs, radius_wc, *flows):
-        radius, wc = radius_wc           # (window radius, warp convention code)
+    def forward(ctx, batch_imgs, cfg, *flows):
+        pw, cw, sw = cfg.pw, cfg.cw, cfg.sw
         _check_dev(batch_imgs, *flows)
-        assert 1 <= len(flows) <= 8
+        ns = len(flows)
+        assert 1 <= ns <= 8, "the loss kernels take 8 levels"
+        assert (ns if pw else 0) + (cw != 0) + (sw != 0) <= 8, \
+            "of_sum_partials takes 8 groups: one per photometric level, census, smoothness"
         fl = [f.contiguous() for f in flows]
         n = fl[0].shape[0]
-        pyr = _pyramid6(batch_imgs.contiguous(), fl)
-        coefs = _census_coefs(n, [f.shape[1] for f in fl], [f.shape[2] for f in fl], 1.0)
-        parts, planes = _census_fwd(pyr, fl, radius, coefs, any(ctx.needs_input_grad[2:]), wc)
-        out = torch.empty((), device=parts.device)
-        call("of_sum_partials", _arr(C.c_void_p, [parts.data_ptr()]),
-             _arr(C.c_int, [parts.numel()]), _arr(C.c_float, [1.0]), 1, _ptr(out), _stream())
-        ctx.save_for_backward(*(planes or []))
-        ctx.coefs = coefs
-        return out
+        hs = [f.shape[1] for f in fl]
+        ws_ = [f.shape[2] for f in fl]
+        want_grad = any(ctx.needs_input_grad[2:])
+        pyr = []
+        if pw != 0 or cw != 0 or cfg.edge_alpha != 0:
+            pyr = _pyramid6(batch_imgs.contiguous(), fl)
+        # The sum's groups are raw (pointer, count, coefficient): ``keep`` holds the partial
+        # arrays until the sum is enqueued.  A dropped one's memory could be handed to the next
+        # term's partials or to ``loss`` and be overwritten ahead of the sum on this stream.
+        groups, keep = [], []
+        coefs = ccoefs = cv = ch = planes = None    # of the terms that are off
+        if pw != 0:
+            coefs = [pw / (ns * n * h * w * 3) for h, w in zip(hs, ws_)]
+            parts, nparts = _photo_fwd(pyr, fl, cfg.wts, cfg.wc)
+            off = 0
+            for k in range(ns):
+                groups.append((parts.data_ptr() + 4 * off, nparts[k], coefs[k]))
+                off += nparts[k]
+            keep.append(parts)
+        # the census and smoothness partials carry their coefficients: one group each
+        if cw != 0:
+            ccoefs = _census_coefs(n, hs, ws_, cw)
+            cparts, planes = _census_fwd(pyr, fl, cfg.radius, ccoefs, want_grad, cfg.wc, cfg.wts)
+            groups.append((cparts.data_ptr(), cparts.numel(), 1.0))
+            keep.append(cparts)
+        if sw != 0:
+            cv, ch = _smooth_coefs(n, hs, ws_, sw)
+            sparts = _smooth_fwd(pyr, fl, cfg.edge_alpha, cfg.eps, cv, ch)
+            groups.append((sparts.data_ptr(), sparts.numel(), 1.0))
+            keep.append(sparts)
+        loss = torch.empty((), device=fl[0].device)
+        call("of_sum_partials", _arr(C.c_void_p, [g[0] for g in groups]),
+             _arr(C.c_int, [g[1] for g in groups]), _arr(C.c_float, [g[2] for g in groups]),
+             len(groups), _ptr(loss), _stream())
+        # Saved: only what a backward of a term that is on reads.  The pyramid: photometric,
+        # and smoothness with edge_alpha != 0; the flows: photometric and smoothness; census
+        # alone keeps just its planes.
+        keep_pyr = pyr if pw != 0 or (sw != 0 and cfg.edge_alpha != 0) else []
+        keep_fl = fl if pw != 0 or sw != 0 else []
+        ctx.save_for_backward(*keep_pyr, *keep_fl, *(planes or []))
+        ctx.split = (len(keep_pyr), len(keep_pyr) + len(keep_fl))
+        ctx.wts = cfg.wts if pw != 0 else None      # the photometric backward reads them again
+        ctx.cfg = cfg._replace(wts=None)
+        ctx.coefs = (coefs, ccoefs, cv, ch)
+        return loss
 
     @staticmethod
     def backward(ctx, dloss):
-        planes = ctx.saved_tensors
+        cfg = ctx.cfg
+        coefs, ccoefs, cv, ch = ctx.coefs
+        saved = ctx.saved_tensors
+        a, b = ctx.split
+        pyr, flows, planes = saved[:a], saved[a:b], saved[b:]
         dloss = dloss.contiguous()
-        grads, lv = [], []
-        for k in range(len(ctx.coefs)):
-            if not ctx.needs_input_grad[2 + k]:
-                grads.append(None)
-                continue
-            df = torch.empty_like(planes[k])
-            grads.append(df)
-            lv.append((k, df, 2))
+        grads, lv = _grad_targets(cfg.fgs, flows or planes, ctx.needs_input_grad[2:])
         if lv:
-            _census_bwd(planes, lv, ctx.coefs, dloss, 0)
+            written = 0                # the first term present writes, the others add
+            if cfg.pw != 0:
+                _photo_bwd(pyr, flows, ctx.wts, lv, coefs, dloss, cfg.wc)
+                written = 1
+            if cfg.cw != 0:
+                _census_bwd(planes, lv, ccoefs, dloss, written)
+                written = 1
+            if cfg.sw != 0:
+                _smooth_bwd(pyr, flows, lv, cfg.edge_alpha, cfg.eps, cv, ch, dloss, written)
         return (None, None, *grads)
+
+
+def photometric_loss(batch_imgs, flows, convention="reference"):
+    """LossLayer.__call__ (loss.py:5-32): mean over scales of mean |img1_s - warp(img2_s)|."""
+    cfg = _LossCfg(pw=1.0, wc=warp_convention(convention), fgs=_flowgrads(flows))
+    return _Loss.apply(batch_imgs, cfg, *flows)
+
+
+def flow_loss(batch_imgs, flows, smoothness_weight, edge_alpha=0.0, eps=1e-4,
+              convention="reference"):
+    """The training loss with the smoothness regulariser: photometric_loss plus
+    ``smoothness_weight`` times flow_smoothness, in one Function (see _Loss)."""
+    cfg = _LossCfg(pw=1.0, sw=float(smoothness_weight), edge_alpha=float(edge_alpha),
+                   eps=float(eps), wc=warp_convention(convention), fgs=_flowgrads(flows))
+    return _Loss.apply(batch_imgs, cfg, *flows)
+
+
+# The two stand-alone terms pass no FlowGrads, even for flows that carry one: a caller who
+# adds two stand-alone terms would have both write the flow head's buffer, the second over
+# the first, where the FlowGrad protocol has the loss write it once.  They return fresh
+# (n,h,w,2) gradients and autograd sums them as usual.
+def flow_smoothness(batch_imgs, flows, edge_alpha=0.0, eps=1e-4):
+    """The smoothness term alone (a scalar; plain gradients for the flows).  The image
+    pyramid is only built when ``edge_alpha`` is not 0."""
+    cfg = _LossCfg(sw=1.0, edge_alpha=float(edge_alpha), eps=float(eps))
+    return _Loss.apply(batch_imgs, cfg, *flows)
 
 
 def _census_radius(radius):
@@ -2511,133 +2452,8 @@ def _census_radius(radius):
 
 def census_loss(batch_imgs, flows, radius=3, convention="reference"):
     """The census term alone (a scalar; plain gradients for the flows)."""
-    return _Census.apply(batch_imgs, (_census_radius(radius), warp_convention(convention)),
-                         *flows)
-
-
-class _CensusFlowLoss(torch.autograd.Function):
-    """photometric_weight * photometric + census_weight * census + smoothness_weight *
-    smoothness on one image pyramid; a term whose weight is 0 launches nothing.  One Function
-    for all terms because of the FlowGrad protocol (see _FlowLoss): in the backward the first
-    term present overwrites each level's d(flow) output and the later ones add into it.
-    ``cfg`` may end with per-level pixel weights of the two data terms ((n,h,w) tensors,
-    constants: occlusion masks), which route them to the ``_w`` kernels; the smoothness term
-    is not weighted."""
-
-    @staticmethod
-    def forward(ctx, batch_imgs, fgs, cfg, *flows):
-        pw, cw, radius, sw, edge_alpha, eps, wc, wts = cfg
-        _check_dev(batch_imgs, *flows)
-        ctx.wc = wc
-        assert pw != 0 or cw != 0, "a data term is needed: both data weights are 0"
-        ctx.fgs = fgs
-        b = batch_imgs.contiguous()
-        n = b.shape[0]
-        ns = len(flows)
-        if cw != 0 and sw != 0:
-            assert 1 <= ns <= 6, "of_sum_partials takes 8 groups: 6 levels, census, smoothness"
-        else:
-            assert 1 <= ns <= 7, "of_sum_partials takes 8 groups: 7 levels and one more term"
-        s = _stream()
-        fl = [f.contiguous() for f in flows]
-        pyr = _pyramid6(b, fl)
-        hs = [p.shape[1] for p in pyr]
-        ws_ = [p.shape[2] for p in pyr]
-        groups = []
-        keep = []                       # partial arrays stay alive until the sum is enqueued
-        coefs = [pw / (ns * n * h * w * 3) for h, w in zip(hs, ws_)]
-        if pw != 0:
-            nparts = [_lib.lib().of_photo_l1_partials(n, h, w) for h, w in zip(hs, ws_)]
-            parts = torch.empty(sum(nparts), device=b.device)
-            if wts is not None:
-                call("of_photo_l1_fwd_multi_w", _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
-                     _arr(C.c_void_p, [f.data_ptr() for f in fl]), _opt_ptrs(wts), n,
-                     _arr(C.c_int, hs), _arr(C.c_int, ws_), ns, _ptr(parts), wc, s)
-            else:
-                _call_cv("of_photo_l1_fwd_multi", wc,
-                         _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
-                         _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs),
-                         _arr(C.c_int, ws_), ns, _ptr(parts), s)
-            off = 0
-            for k in range(ns):
-                groups.append((parts.data_ptr() + 4 * off, nparts[k], coefs[k]))
-                off += nparts[k]
-            keep.append(parts)
-        # the census and smoothness partials carry their coefficients: one group each
-        ccoefs = _census_coefs(n, hs, ws_, cw)
-        planes = None
-        if cw != 0:
-            cparts, planes = _census_fwd(pyr, fl, radius, ccoefs, any(ctx.needs_input_grad[3:]),
-                                         wc, wts)
-            groups.append((cparts.data_ptr(), cparts.numel(), 1.0))
-            keep.append(cparts)
-        cv, ch = _smooth_coefs(n, hs, ws_, sw)
-        if sw != 0:
-            sparts = _smooth_fwd(pyr, fl, edge_alpha, eps, cv, ch)
-            groups.append((sparts.data_ptr(), sparts.numel(), 1.0))
-            keep.append(sparts)
-        loss = torch.empty((), device=b.device)
-        call("of_sum_partials", _arr(C.c_void_p, [g[0] for g in groups]),
-             _arr(C.c_int, [g[1] for g in groups]), _arr(C.c_float, [g[2] for g in groups]),
-             len(groups), _ptr(loss), s)
-        ctx.save_for_backward(*pyr, *fl, *(planes or []))
-        ctx.wts = wts if pw != 0 else None      # the photometric backward reads them again
-        ctx.cfg = (ns, pw, cw, sw, edge_alpha, eps, coefs, ccoefs, cv, ch)
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        ns, pw, cw, sw, edge_alpha, eps, coefs, ccoefs, cv, ch = ctx.cfg
-        saved = ctx.saved_tensors
-        pyr, flows, planes = saved[:ns], saved[ns:2 * ns], saved[2 * ns:]
-        dloss = dloss.contiguous()
-        s = _stream()
-        grads, lv = [], []          # lv: (level, output, row stride) of one multi launch
-        for k in range(ns):
-            if not ctx.needs_input_grad[3 + k]:
-                grads.append(None)
-                continue
-            fg = ctx.fgs[k]
-            if fg is not None:         # into the flow head's padded gradient (FlowGrad)
-                buf = fg.buffer()
-                fg.filled = True
-                grads.append(buf[..., :2])
-                lv.append((k, buf, 4))
-                continue
-            df = torch.empty_like(flows[k])
-            grads.append(df)
-            lv.append((k, df, 2))
-        if lv:
-            m = len(lv)
-            n = pyr[0].shape[0]
-            written = 0                # the first term present writes, the others add
-            if pw != 0 and ctx.wts is not None:
-                call("of_photo_l1_bwd_multi_w",
-                     _arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]),
-                     _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]),
-                     _opt_ptrs([ctx.wts[k] for k, _, _ in lv]), n,
-                     _arr(C.c_int, [pyr[k].shape[1] for k, _, _ in lv]),
-                     _arr(C.c_int, [pyr[k].shape[2] for k, _, _ in lv]), m,
-                     _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
-                     _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
-                     _arr(C.c_int, [ld for _, _, ld in lv]), ctx.wc, s)
-                written = 1
-            elif pw != 0:
-                _call_cv("of_photo_l1_bwd_multi", ctx.wc,
-                         _arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]),
-                         _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]), n,
-                         _arr(C.c_int, [pyr[k].shape[1] for k, _, _ in lv]),
-                         _arr(C.c_int, [pyr[k].shape[2] for k, _, _ in lv]), m,
-                         _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
-                         _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
-                         _arr(C.c_int, [ld for _, _, ld in lv]), s)
-                written = 1
-            if cw != 0:
-                _census_bwd(planes, lv, ccoefs, dloss, written)
-                written = 1
-            if sw != 0:
-                _smooth_bwd(pyr, flows, lv, edge_alpha, eps, cv, ch, dloss, written)
-        return (None, None, None, *grads)
+    cfg = _LossCfg(cw=1.0, radius=_census_radius(radius), wc=warp_convention(convention))
+    return _Loss.apply(batch_imgs, cfg, *flows)
 
 
 def _pixel_weights(weights, flows):
@@ -2662,21 +2478,20 @@ def census_flow_loss(batch_imgs, flows, census_weight, census_radius=3, photomet
                      weights=None):
     """The training loss with the census data term: ``photometric_weight`` times
     photometric_loss plus ``census_weight`` times census_loss plus ``smoothness_weight`` times
-    flow_smoothness, in one Function (see _CensusFlowLoss).  At least one data weight must be
+    flow_smoothness, in one Function (see _Loss).  At least one data weight must be
     non-zero; the kernels of a term whose weight is 0 are not launched.
 
     ``weights``: per level a (n,h,w) tensor of non-negative pixel weights for the two data
     terms (occlusion_masks' output, or None for a level of weight 1).  They are constants; a
     pixel's photometric error and its census window sum are multiplied by its weight, the
     normalisers stay the means over all pixels, and the smoothness term is not weighted."""
-    fgs = [getattr(f, "_of_flowgrad", None) for f in flows]
-    if any(fg is not None and fg.shape != tuple(f.shape) for fg, f in zip(fgs, flows)):
-        fgs = [None] * len(flows)
     wts = _pixel_weights(weights, flows) if weights is not None else None
-    cfg = (float(photometric_weight), float(census_weight), _census_radius(census_radius),
-           float(smoothness_weight), float(edge_alpha), float(eps), warp_convention(convention),
-           wts)
-    return _CensusFlowLoss.apply(batch_imgs, fgs, cfg, *flows)
+    cfg = _LossCfg(pw=float(photometric_weight), cw=float(census_weight),
+                   radius=_census_radius(census_radius), sw=float(smoothness_weight),
+                   edge_alpha=float(edge_alpha), eps=float(eps),
+                   wc=warp_convention(convention), wts=wts, fgs=_flowgrads(flows))
+    assert cfg.pw != 0 or cfg.cw != 0, "a data term is needed: both data weights are 0"
+    return _Loss.apply(batch_imgs, cfg, *flows)
 
 
 # ============================================================== occlusion masks =====
