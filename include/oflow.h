@@ -424,6 +424,33 @@ int of_flow_smooth_bwd_multi(const float* const* img6s, const float* const* flow
                              const float* dloss, float* const* dflows, const int* lds,
                              int accumulate, void* stream);
 
+/* Edge-aware second-order flow smoothness: the same arguments, row-stride and accumulate rules,
+ * partials protocol and OF_EINVAL cases as the first-order entries above, for the sums
+ *   d2v[b,i,j,c] = f[b,i-1,j,c] - 2 f[b,i,j,c] + f[b,i+1,j,c]     1 <= i <= h-2
+ *   d2h[b,i,j,c] = f[b,i,j-1,c] - 2 f[b,i,j,c] + f[b,i,j+1,c]     1 <= j <= w-2
+ *   wv2[b,i,j]   = exp(-edge_alpha * mean_{c<3} |img[b,i-1,j,c] - img[b,i+1,j,c]|)
+ *   wh2[b,i,j]   = exp(-edge_alpha * mean_{c<3} |img[b,i,j-1,c] - img[b,i,j+1,c]|)
+ *   Sv2 = sum over (b, centres, c<2) of wv2 * rho(d2v),   Sh2 likewise with wh2, d2h
+ * (the weight spans the triple's two outer pixels; 1 when edge_alpha == 0, img6s may then be
+ * NULL and no image byte is read).  No triple crosses a row end or an image boundary; a
+ * direction with h < 3 (w < 3) has no triple, its sum and gradient are exactly 0.  Level l's
+ * partial slice sums to coefs_v[l]*Sv2 + coefs_h[l]*Sh2; the backward is d(flow) of the sum over
+ * levels of that, a gather: with t = w2 * d2 / sqrt(d2*d2 + eps) at each centre, a pixel gets
+ * t[p-1] - 2 t[p] + t[p+1] per direction over the centres that exist.  Both kernels stage an
+ * 8 x 32 pixel tile plus halo in LDS, one workgroup per tile (image-major, then tile row, then
+ * tile column), one partial per workgroup: of_flow_smooth2_partials = n * ceil(h/8) *
+ * ceil(w/32) (0 for a non-positive size).  No atomics: run-to-run bitwise equal. */
+int of_flow_smooth2_partials(int n, int h, int w);
+int of_flow_smooth2_fwd_multi(const float* const* img6s, const float* const* flows, int n,
+                              const int* hs, const int* ws, int levels, float edge_alpha,
+                              float eps, const float* coefs_v, const float* coefs_h,
+                              float* partials, void* stream);
+int of_flow_smooth2_bwd_multi(const float* const* img6s, const float* const* flows, int n,
+                              const int* hs, const int* ws, int levels, float edge_alpha,
+                              float eps, const float* coefs_v, const float* coefs_h,
+                              const float* dloss, float* const* dflows, const int* lds,
+                              int accumulate, void* stream);
+
 /* Soft ternary census data term (illumination-robust), every level in one launch (levels <= 8;
  * level l holds img6s[l] (n,hs[l],ws[l],6), of_pyramid6's output -- channels 0..2 image 1,
  * 3..5 image 2 -- and flows[l] (n,hs[l],ws[l],2)).  With S = 255, c_t = 0.81, c_d = 0.1,

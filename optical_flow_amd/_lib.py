@@ -194,6 +194,12 @@ PROTOTYPES = {
     "of_flow_smooth_bwd_multi": (I, [C.POINTER(P), C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I,
                                      F, F, C.POINTER(F), C.POINTER(F), P, C.POINTER(P),
                                      C.POINTER(I), I, P]),
+    "of_flow_smooth2_partials": (I, [I, I, I]),
+    "of_flow_smooth2_fwd_multi": (I, [C.POINTER(P), C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I,
+                                      F, F, C.POINTER(F), C.POINTER(F), P, P]),
+    "of_flow_smooth2_bwd_multi": (I, [C.POINTER(P), C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I,
+                                      F, F, C.POINTER(F), C.POINTER(F), P, C.POINTER(P),
+                                      C.POINTER(I), I, P]),
     "of_census_partials": (I, [I, I, I]),
     "of_census_workspace_floats": (I, [I, I, I]),
     "of_census_fwd_multi": (I, [C.POINTER(P), C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I, I,

@@ -3,6 +3,11 @@
 // one launch.  Same shape as the photo_l1_*_multi pair (flow_ops.hip): the forward writes one
 // partial per block for of_sum_partials, the backward is a gather (each pixel sums the
 // derivative of its four edges), so neither uses atomics and both are run-to-run bitwise equal.
+//
+// The second-order term (flow_smooth2_*_multi, below) penalises the flow's second differences
+// f[p-1] - 2 f[p] + f[p+1] per direction, weighted by the image difference across the triple's
+// two outer pixels.  Its stencil is five pixels wide per direction in the backward, so both of
+// its kernels stage an 8 x 32 pixel tile plus halo in LDS (the shape of census_loss.hip).
 #include <algorithm>
 
 #include "common.h"
@@ -174,6 +179,188 @@ static int smooth_args(const char* fn, const float* const* img6s, const float* c
   return OF_OK;
 }
 
+// ---------------------------------------------------------------- second order ----
+constexpr int S2_TY = 8, S2_TX = 32, S2_THREADS = S2_TY * S2_TX;
+
+// The tile grid of each level.  Level l's workgroups are [beg[l], beg[l+1]) of SmoothMulti in
+// both kernels: image-major, then tile row, then tile column.
+struct Smooth2Tiles {
+  int tx[8], ty[8];
+};
+
+// Second difference of a triple (outer, centre, outer), products rounded on their own so that
+// forward and backward form the same value.
+__device__ __forceinline__ float2 smooth2_d2(float2 a, float2 b, float2 c) {
+#pragma clang fp contract(off)
+  return make_float2((a.x - 2.f * b.x) + c.x, (a.y - 2.f * b.y) + c.y);
+}
+
+// The halo tile of one workgroup in LDS: flows as float2, image 1 as three planes (EDGE only).
+// Positions outside the image hold 0 and are never used: every triple is masked by its
+// centre's coordinates.
+template <bool EDGE, int HALO>
+struct Smooth2Tile {
+  static constexpr int HW = S2_TX + 2 * HALO, HH = S2_TY + 2 * HALO, N = HH * HW;
+  float2 f[N];
+  float i[EDGE ? 3 : 1][EDGE ? N : 1];
+
+  __device__ __forceinline__ void load(const float* __restrict__ img6,
+                                       const float* __restrict__ flow, int64_t img, int y0,
+                                       int x0, int h, int w) {
+    for (int k = threadIdx.x; k < N; k += S2_THREADS) {
+      const int y = y0 - HALO + k / HW, x = x0 - HALO + k % HW;
+      float2 v = make_float2(0.f, 0.f);
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+      if (y >= 0 && y < h && x >= 0 && x < w) {
+        const int64_t p = img + (int64_t)y * w + x;
+        v = flow_at(flow, p);
+        if (EDGE) a0 = img6[p * 6], a1 = img6[p * 6 + 1], a2 = img6[p * 6 + 2];
+      }
+      f[k] = v;
+      if (EDGE) i[0][k] = a0, i[1][k] = a1, i[2][k] = a2;
+    }
+  }
+
+  // weight of the triple whose outer pixels are LDS positions p and q
+  __device__ __forceinline__ float weight(int p, int q, float alpha) const {
+    if (!EDGE) return 1.f;
+    const float m = (fabsf(i[0][p] - i[0][q]) + fabsf(i[1][p] - i[1][q]) +
+                     fabsf(i[2][p] - i[2][q])) * (1.f / 3.f);
+    return __expf(-alpha * m);
+  }
+};
+
+// which workgroup of which level: (level, image offset in pixels, tile origin)
+__device__ __forceinline__ int smooth2_tile(const SmoothMulti& m, const Smooth2Tiles& g,
+                                            int64_t& img, int& y0, int& x0) {
+  int l = 0;
+  while (l + 1 < m.levels && (int64_t)blockIdx.x >= m.beg[l + 1]) ++l;
+  int t = (int)((int64_t)blockIdx.x - m.beg[l]);
+  x0 = (t % g.tx[l]) * S2_TX;
+  t /= g.tx[l];
+  y0 = (t % g.ty[l]) * S2_TY;
+  img = (int64_t)(t / g.ty[l]) * m.h[l] * m.w[l];
+  return l;
+}
+
+template <bool EDGE>
+__global__ __launch_bounds__(S2_THREADS) void flow_smooth2_fwd_multi(
+    SmoothMulti m, Smooth2Tiles g, float alpha, float eps, float* __restrict__ partials) {
+  using Tile = Smooth2Tile<EDGE, 1>;
+  __shared__ Tile s;
+  __shared__ float red[S2_THREADS / 64];
+  int64_t img;
+  int y0, x0;
+  const int l = smooth2_tile(m, g, img, y0, x0);
+  const int h = m.h[l], w = m.w[l];
+  s.load(m.img6[l], m.flow[l], img, y0, x0, h, w);
+  __syncthreads();
+
+  // each pixel of the tile is the centre of (at most) one vertical and one horizontal triple
+  const int ly = threadIdx.x / S2_TX, lx = threadIdx.x % S2_TX;
+  const int y = y0 + ly, x = x0 + lx;
+  const int c = (ly + 1) * Tile::HW + lx + 1;
+  float r = 0.f;
+  if (y < h && x < w) {
+    const float2 f = s.f[c];
+    if (y >= 1 && y + 1 < h) {
+      const float2 d = smooth2_d2(s.f[c - Tile::HW], f, s.f[c + Tile::HW]);
+      r += m.cv[l] * s.weight(c - Tile::HW, c + Tile::HW, alpha) *
+           (sqrtf(d.x * d.x + eps) + sqrtf(d.y * d.y + eps));
+    }
+    if (x >= 1 && x + 1 < w) {      // never across a row end
+      const float2 d = smooth2_d2(s.f[c - 1], f, s.f[c + 1]);
+      r += m.ch[l] * s.weight(c - 1, c + 1, alpha) *
+           (sqrtf(d.x * d.x + eps) + sqrtf(d.y * d.y + eps));
+    }
+  }
+  // block reduction in a fixed order: wave shuffles then LDS
+  for (int o = 32; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = r;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int k = 0; k < S2_THREADS / 64; ++k) t += red[k];
+    partials[blockIdx.x] = t;
+  }
+}
+
+// t = w2 * rho'(d2) of one triple, both channels
+__device__ __forceinline__ float2 smooth2_t(float2 d, float wt, float eps) {
+  return make_float2(wt * d.x * rsqrtf(d.x * d.x + eps), wt * d.y * rsqrtf(d.y * d.y + eps));
+}
+
+template <bool EDGE>
+__global__ __launch_bounds__(S2_THREADS) void flow_smooth2_bwd_multi(
+    SmoothMulti m, Smooth2Tiles g, float alpha, float eps, const float* __restrict__ dloss,
+    int accumulate) {
+  using Tile = Smooth2Tile<EDGE, 2>;
+  constexpr int HW = Tile::HW;
+  constexpr int NV = (S2_TY + 2) * S2_TX;       // vertical centres: the tile's rows -1 .. TY
+  constexpr int TW = S2_TX + 2, NH = S2_TY * TW;    // horizontal ones: its columns -1 .. TX
+  __shared__ Tile s;
+  __shared__ float2 tv[NV], th[NH];
+  int64_t img;
+  int y0, x0;
+  const int l = smooth2_tile(m, g, img, y0, x0);
+  const int h = m.h[l], w = m.w[l];
+  s.load(m.img6[l], m.flow[l], img, y0, x0, h, w);
+  __syncthreads();
+
+  // every triple's t once; a centre that has no triple (outside the image, or in its first or
+  // last row / column) gets 0, so the gather below needs no case of its own
+  for (int k = threadIdx.x; k < NV + NH; k += S2_THREADS) {
+    float2 t = make_float2(0.f, 0.f);
+    if (k < NV) {
+      const int r = k / S2_TX, cc = k % S2_TX;
+      const int y = y0 - 1 + r, x = x0 + cc;
+      const int c = (r + 1) * HW + cc + 2;
+      if (y >= 1 && y + 1 < h && x < w)
+        t = smooth2_t(smooth2_d2(s.f[c - HW], s.f[c], s.f[c + HW]),
+                      s.weight(c - HW, c + HW, alpha), eps);
+      tv[k] = t;
+    } else {
+      const int r = (k - NV) / TW, cc = (k - NV) % TW;
+      const int y = y0 + r, x = x0 - 1 + cc;
+      const int c = (r + 2) * HW + cc + 1;
+      if (y < h && x >= 1 && x + 1 < w)
+        t = smooth2_t(smooth2_d2(s.f[c - 1], s.f[c], s.f[c + 1]), s.weight(c - 1, c + 1, alpha),
+                      eps);
+      th[k - NV] = t;
+    }
+  }
+  __syncthreads();
+
+  const int ly = threadIdx.x / S2_TX, lx = threadIdx.x % S2_TX;
+  const int y = y0 + ly, x = x0 + lx;
+  if (y >= h || x >= w) return;
+  // this pixel is an outer pixel of the triples centred one step either side, the centre of its own
+  const float2 va = tv[ly * S2_TX + lx], vb = tv[(ly + 1) * S2_TX + lx],
+               vc = tv[(ly + 2) * S2_TX + lx];
+  const float2 ha = th[ly * TW + lx], hb = th[ly * TW + lx + 1], hc = th[ly * TW + lx + 2];
+  const float dl = dloss ? dloss[0] : 1.f;
+  const float cv = m.cv[l] * dl, ch = m.ch[l] * dl;
+  float gx = cv * (va.x - 2.f * vb.x + vc.x) + ch * (ha.x - 2.f * hb.x + hc.x);
+  float gy = cv * (va.y - 2.f * vb.y + vc.y) + ch * (ha.y - 2.f * hb.y + hc.y);
+  // channels 2.. of a padded row: untouched
+  float* d = m.dflow[l] + (int64_t)m.ld[l] * (img + (int64_t)y * w + x);
+  if (accumulate) gx += d[0], gy += d[1];
+  d[0] = gx;
+  d[1] = gy;
+}
+
+// The tile table of both second-order entries (after smooth_args): beg[] and the grid.
+static int smooth2_tiles(const std::string& f, int n, SmoothMulti& m, Smooth2Tiles& g) {
+  m.beg[0] = 0;
+  for (int l = 0; l < m.levels; ++l) {
+    g.tx[l] = (int)cdiv(m.w[l], S2_TX);
+    g.ty[l] = (int)cdiv(m.h[l], S2_TY);
+    m.beg[l + 1] = m.beg[l] + (int64_t)n * g.ty[l] * g.tx[l];
+  }
+  if (m.beg[m.levels] >= INT32_MAX) return fail(OF_EINVAL, f + ": too many blocks");
+  return OF_OK;
+}
+
 }  // namespace oflow
 
 using namespace oflow;
@@ -236,6 +423,60 @@ int of_flow_smooth_bwd_multi(const float* const* img6s, const float* const* flow
     hipLaunchKernelGGL(flow_smooth_bwd_multi<false>, grid, block, 0, as_stream(stream), n, m,
                        edge_alpha, eps, dloss, accumulate);
   return check_launch("flow_smooth_bwd_multi");
+}
+
+int of_flow_smooth2_partials(int n, int h, int w) {
+  if (n < 1 || h < 1 || w < 1) return 0;
+  return (int)std::min<int64_t>(n * cdiv(h, S2_TY) * cdiv(w, S2_TX), INT32_MAX);
+}
+
+int of_flow_smooth2_fwd_multi(const float* const* img6s, const float* const* flows, int n,
+                              const int* hs, const int* ws, int levels, float edge_alpha,
+                              float eps, const float* coefs_v, const float* coefs_h,
+                              float* partials, void* stream) {
+  static const char* fn = "of_flow_smooth2_fwd_multi";
+  SmoothMulti m{};
+  Smooth2Tiles g{};
+  int st = smooth_args(fn, img6s, flows, n, hs, ws, levels, edge_alpha, eps, coefs_v, coefs_h, m);
+  if (st) return st;
+  if (!partials) return fail(OF_EINVAL, std::string(fn) + ": NULL partials");
+  if ((st = smooth2_tiles(fn, n, m, g))) return st;
+  const dim3 grid((unsigned)m.beg[levels]), block(S2_THREADS);
+  if (edge_alpha != 0.f)
+    hipLaunchKernelGGL(flow_smooth2_fwd_multi<true>, grid, block, 0, as_stream(stream), m, g,
+                       edge_alpha, eps, partials);
+  else
+    hipLaunchKernelGGL(flow_smooth2_fwd_multi<false>, grid, block, 0, as_stream(stream), m, g,
+                       edge_alpha, eps, partials);
+  return check_launch("flow_smooth2_fwd_multi");
+}
+
+int of_flow_smooth2_bwd_multi(const float* const* img6s, const float* const* flows, int n,
+                              const int* hs, const int* ws, int levels, float edge_alpha,
+                              float eps, const float* coefs_v, const float* coefs_h,
+                              const float* dloss, float* const* dflows, const int* lds,
+                              int accumulate, void* stream) {
+  static const char* fn = "of_flow_smooth2_bwd_multi";
+  SmoothMulti m{};
+  Smooth2Tiles g{};
+  int st = smooth_args(fn, img6s, flows, n, hs, ws, levels, edge_alpha, eps, coefs_v, coefs_h, m);
+  if (st) return st;
+  if (!dflows || !lds) return fail(OF_EINVAL, std::string(fn) + ": NULL argument");
+  for (int l = 0; l < levels; ++l) {
+    if (!dflows[l]) return fail(OF_EINVAL, std::string(fn) + ": NULL dflow");
+    if (lds[l] < 2) return fail(OF_EINVAL, std::string(fn) + ": lds[l] must be >= 2");
+    m.dflow[l] = dflows[l];
+    m.ld[l] = lds[l];
+  }
+  if ((st = smooth2_tiles(fn, n, m, g))) return st;
+  const dim3 grid((unsigned)m.beg[levels]), block(S2_THREADS);
+  if (edge_alpha != 0.f)
+    hipLaunchKernelGGL(flow_smooth2_bwd_multi<true>, grid, block, 0, as_stream(stream), m, g,
+                       edge_alpha, eps, dloss, accumulate);
+  else
+    hipLaunchKernelGGL(flow_smooth2_bwd_multi<false>, grid, block, 0, as_stream(stream), m, g,
+                       edge_alpha, eps, dloss, accumulate);
+  return check_launch("flow_smooth2_bwd_multi");
 }
 
 }  // extern "C"

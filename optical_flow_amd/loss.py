@@ -15,6 +15,10 @@ class LossLayer:
     Charbonnier penalty sqrt(d^2 + smoothness_eps) of the vertical plus that of the horizontal
     first differences, each weighted by exp(-edge_alpha * mean |d image1|) across the same
     pixel pair, averaged over scales (ops.flow_loss; DESIGN.md has the definition).
+    ``smoothness_order`` = 2 (build-added) penalises the second differences f[p-1] - 2 f[p] +
+    f[p+1] instead, weighted across each triple's two outer pixels: a flow that is affine in
+    image coordinates (a plane seen in perspective) then costs nothing (DESIGN.md
+    "Second-order smoothness").  It plays no part while ``smoothness_weight`` is 0.
 
     ``census_weight`` > 0 (build-added) adds that weight times the soft ternary census term,
     an illumination-robust data term that compares the local intensity order of image 1 and
@@ -39,7 +43,7 @@ class LossLayer:
     def __init__(self, smoothness_weight=0.0, edge_alpha=0.0, smoothness_eps=1e-4,
                  census_weight=0.0, census_radius=3, photometric_weight=1.0,
                  warp_convention="reference", occlusion="none", occlusion_alpha1=0.01,
-                 occlusion_alpha2=0.5):
+                 occlusion_alpha2=0.5, smoothness_order=1):
         ops.warp_convention(warp_convention)
         self.warp_convention = warp_convention
         if occlusion not in ("none", "border", "fb"):
@@ -69,6 +73,9 @@ class LossLayer:
         if census_weight == 0 and photometric_weight == 0:
             raise ValueError("census_weight and photometric_weight are both 0: the loss needs "
                              "a data term")
+        if smoothness_order not in (1, 2) or isinstance(smoothness_order, bool):
+            raise ValueError("smoothness_order must be 1 or 2, got %r" % (smoothness_order,))
+        self.smoothness_order = int(smoothness_order)
         self.smoothness_weight = float(smoothness_weight)
         self.edge_alpha = float(edge_alpha)
         self.smoothness_eps = float(smoothness_eps)
@@ -85,6 +92,8 @@ class LossLayer:
             assert flows[scale_idx].shape[1] == scaled_height
             assert flows[scale_idx].shape[2] == scaled_width
         assert batch_imgs.shape[3] == 6
+        # the first order is the ops entries' default: such a layer calls them as it always did
+        order = {"smoothness_order": 2} if self.smoothness_order == 2 else {}
         if self.occlusion != "none":
             if self.occlusion == "fb" and batch_imgs.shape[0] % 2:
                 raise ValueError("occlusion='fb' scores the doubled batch [pairs ; swapped "
@@ -96,13 +105,15 @@ class LossLayer:
             return ops.census_flow_loss(batch_imgs, list(flows), self.census_weight,
                                         self.census_radius, self.photometric_weight,
                                         self.smoothness_weight, self.edge_alpha,
-                                        self.smoothness_eps, self.warp_convention, weights=masks)
+                                        self.smoothness_eps, self.warp_convention, weights=masks,
+                                        **order)
         if self.census_weight == 0.0 and self.photometric_weight == 1.0:
             if self.smoothness_weight == 0.0:
                 return ops.photometric_loss(batch_imgs, list(flows), self.warp_convention)
             return ops.flow_loss(batch_imgs, list(flows), self.smoothness_weight,
-                                 self.edge_alpha, self.smoothness_eps, self.warp_convention)
+                                 self.edge_alpha, self.smoothness_eps, self.warp_convention,
+                                 **order)
         return ops.census_flow_loss(batch_imgs, list(flows), self.census_weight,
                                     self.census_radius, self.photometric_weight,
                                     self.smoothness_weight, self.edge_alpha,
-                                    self.smoothness_eps, self.warp_convention)
+                                    self.smoothness_eps, self.warp_convention, **order)

@@ -2186,41 +2186,56 @@ def _photo_bwd(pyr, flows, wts, lv, coefs, dloss, wc):
 
 
 # ============================================================== flow smoothness =====
-def _smooth_coefs(n, hs, ws, scale):
+def _smooth_order(order):
+    if order not in (1, 2) or isinstance(order, bool):
+        raise ValueError("smoothness order must be 1 or 2, got %r" % (order,))
+    return int(order)
+
+
+# The C entries of the two orders take the same arguments (include/oflow.h).
+_SMOOTH_ENTRIES = {1: "of_flow_smooth", 2: "of_flow_smooth2"}
+
+
+def _smooth_coefs(n, hs, ws, scale, order=1):
     """The normalisers of the smoothness term, times ``scale``: the mean over each
-    direction's pairs and over the levels; a direction with no pairs contributes 0."""
+    direction's pairs (order 1) or triples (order 2) and over the levels; a direction with
+    none contributes 0."""
     ns = len(hs)
-    cv = [scale / (ns * n * (h - 1) * w * 2) if h > 1 else 0.0 for h, w in zip(hs, ws)]
-    ch = [scale / (ns * n * h * (w - 1) * 2) if w > 1 else 0.0 for h, w in zip(hs, ws)]
+    cv = [scale / (ns * n * (h - order) * w * 2) if h > order else 0.0 for h, w in zip(hs, ws)]
+    ch = [scale / (ns * n * h * (w - order) * 2) if w > order else 0.0 for h, w in zip(hs, ws)]
     return cv, ch
 
 
-def _smooth_fwd(pyr, fl, edge_alpha, eps, cv, ch):
+def _smooth_fwd(pyr, fl, edge_alpha, eps, cv, ch, order=1):
     """of_flow_smooth_fwd_multi over every level (include/oflow.h): the mean Charbonnier
     penalty of the vertical plus that of the horizontal first differences of the flow, each
     weighted by exp(-edge_alpha * mean|d image1|) across the same pair.  Returns the partials
     (they sum to the weighted term, the coefficients are applied in the kernel).  The images
-    are only read when ``edge_alpha`` is not 0."""
+    are only read when ``edge_alpha`` is not 0.  ``order`` 2: of_flow_smooth2_fwd_multi, the
+    second differences, weighted across each triple's two outer pixels."""
     ns = len(fl)
     n = fl[0].shape[0]
     hs = [f.shape[1] for f in fl]
     ws_ = [f.shape[2] for f in fl]
-    nparts = sum(_lib.lib().of_flow_smooth_partials(n, h, w) for h, w in zip(hs, ws_))
+    entry = _SMOOTH_ENTRIES[order]
+    count = getattr(_lib.lib(), entry + "_partials")
+    nparts = sum(count(n, h, w) for h, w in zip(hs, ws_))
     parts = torch.empty(nparts, device=fl[0].device)
     imgs = _arr(C.c_void_p, [p.data_ptr() for p in pyr]) if edge_alpha != 0 else None
-    call("of_flow_smooth_fwd_multi", imgs, _arr(C.c_void_p, [f.data_ptr() for f in fl]), n,
+    call(entry + "_fwd_multi", imgs, _arr(C.c_void_p, [f.data_ptr() for f in fl]), n,
          _arr(C.c_int, hs), _arr(C.c_int, ws_), ns, edge_alpha, eps, _arr(C.c_float, cv),
          _arr(C.c_float, ch), _ptr(parts), _stream())
     return parts
 
 
-def _smooth_bwd(pyr, flows, lv, edge_alpha, eps, cv, ch, dloss, accumulate):
-    """of_flow_smooth_bwd_multi for the levels in ``lv``."""
+def _smooth_bwd(pyr, flows, lv, edge_alpha, eps, cv, ch, dloss, accumulate, order=1):
+    """of_flow_smooth_bwd_multi (``order`` 2: of_flow_smooth2_bwd_multi) for the levels in
+    ``lv``."""
     m = len(lv)
     n = flows[0].shape[0]
     imgs = (_arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]) if edge_alpha != 0
             else None)
-    call("of_flow_smooth_bwd_multi", imgs,
+    call(_SMOOTH_ENTRIES[order] + "_bwd_multi", imgs,
          _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]), n,
          _arr(C.c_int, [flows[k].shape[1] for k, _, _ in lv]),
          _arr(C.c_int, [flows[k].shape[2] for k, _, _ in lv]), m, edge_alpha, eps,
@@ -2321,6 +2336,7 @@ class _LossCfg(NamedTuple):
     radius: int = 3                 # census window radius
     edge_alpha: float = 0.0         # smoothness: edge weighting and the Charbonnier eps
     eps: float = 1e-4
+    order: int = 1                  # smoothness: 1 first differences, 2 second differences
     wc: int = _lib.WARP_REFERENCE   # warp convention code of the data terms
     wts: Optional[list] = None      # per-level pixel weights of the data terms ((n,h,w)
     #                                 tensors, constants: occlusion masks); None: unweighted
@@ -2376,8 +2392,8 @@ class _Loss(torch.autograd.Function):
             groups.append((cparts.data_ptr(), cparts.numel(), 1.0))
             keep.append(cparts)
         if sw != 0:
-            cv, ch = _smooth_coefs(n, hs, ws_, sw)
-            sparts = _smooth_fwd(pyr, fl, cfg.edge_alpha, cfg.eps, cv, ch)
+            cv, ch = _smooth_coefs(n, hs, ws_, sw, cfg.order)
+            sparts = _smooth_fwd(pyr, fl, cfg.edge_alpha, cfg.eps, cv, ch, cfg.order)
             groups.append((sparts.data_ptr(), sparts.numel(), 1.0))
             keep.append(sparts)
         loss = torch.empty((), device=fl[0].device)
@@ -2414,7 +2430,8 @@ class _Loss(torch.autograd.Function):
                 _census_bwd(planes, lv, ccoefs, dloss, written)
                 written = 1
             if cfg.sw != 0:
-                _smooth_bwd(pyr, flows, lv, cfg.edge_alpha, cfg.eps, cv, ch, dloss, written)
+                _smooth_bwd(pyr, flows, lv, cfg.edge_alpha, cfg.eps, cv, ch, dloss, written,
+                            cfg.order)
         return (None, None, *grads)
 
 
@@ -2425,11 +2442,13 @@ def photometric_loss(batch_imgs, flows, convention="reference"):
 
 
 def flow_loss(batch_imgs, flows, smoothness_weight, edge_alpha=0.0, eps=1e-4,
-              convention="reference"):
+              convention="reference", smoothness_order=1):
     """The training loss with the smoothness regulariser: photometric_loss plus
-    ``smoothness_weight`` times flow_smoothness, in one Function (see _Loss)."""
+    ``smoothness_weight`` times flow_smoothness (of ``smoothness_order`` 1 or 2), in one
+    Function (see _Loss)."""
     cfg = _LossCfg(pw=1.0, sw=float(smoothness_weight), edge_alpha=float(edge_alpha),
-                   eps=float(eps), wc=warp_convention(convention), fgs=_flowgrads(flows))
+                   eps=float(eps), order=_smooth_order(smoothness_order),
+                   wc=warp_convention(convention), fgs=_flowgrads(flows))
     return _Loss.apply(batch_imgs, cfg, *flows)
 
 
@@ -2437,10 +2456,12 @@ def flow_loss(batch_imgs, flows, smoothness_weight, edge_alpha=0.0, eps=1e-4,
 # adds two stand-alone terms would have both write the flow head's buffer, the second over
 # the first, where the FlowGrad protocol has the loss write it once.  They return fresh
 # (n,h,w,2) gradients and autograd sums them as usual.
-def flow_smoothness(batch_imgs, flows, edge_alpha=0.0, eps=1e-4):
+def flow_smoothness(batch_imgs, flows, edge_alpha=0.0, eps=1e-4, order=1):
     """The smoothness term alone (a scalar; plain gradients for the flows).  The image
-    pyramid is only built when ``edge_alpha`` is not 0."""
-    cfg = _LossCfg(sw=1.0, edge_alpha=float(edge_alpha), eps=float(eps))
+    pyramid is only built when ``edge_alpha`` is not 0.  ``order`` 1 penalises the flow's
+    first differences, 2 its second differences (DESIGN.md "Second-order smoothness")."""
+    cfg = _LossCfg(sw=1.0, edge_alpha=float(edge_alpha), eps=float(eps),
+                   order=_smooth_order(order))
     return _Loss.apply(batch_imgs, cfg, *flows)
 
 
@@ -2475,10 +2496,11 @@ def _pixel_weights(weights, flows):
 
 def census_flow_loss(batch_imgs, flows, census_weight, census_radius=3, photometric_weight=1.0,
                      smoothness_weight=0.0, edge_alpha=0.0, eps=1e-4, convention="reference",
-                     weights=None):
+                     weights=None, smoothness_order=1):
     """The training loss with the census data term: ``photometric_weight`` times
     photometric_loss plus ``census_weight`` times census_loss plus ``smoothness_weight`` times
-    flow_smoothness, in one Function (see _Loss).  At least one data weight must be
+    flow_smoothness (of ``smoothness_order`` 1 or 2), in one Function (see _Loss).  At least
+    one data weight must be
     non-zero; the kernels of a term whose weight is 0 are not launched.
 
     ``weights``: per level a (n,h,w) tensor of non-negative pixel weights for the two data
@@ -2489,6 +2511,7 @@ def census_flow_loss(batch_imgs, flows, census_weight, census_radius=3, photomet
     cfg = _LossCfg(pw=float(photometric_weight), cw=float(census_weight),
                    radius=_census_radius(census_radius), sw=float(smoothness_weight),
                    edge_alpha=float(edge_alpha), eps=float(eps),
+                   order=_smooth_order(smoothness_order),
                    wc=warp_convention(convention), wts=wts, fgs=_flowgrads(flows))
     assert cfg.pw != 0 or cfg.cw != 0, "a data term is needed: both data weights are 0"
     return _Loss.apply(batch_imgs, cfg, *flows)

@@ -393,6 +393,9 @@ def build_parser():
                     help="weight of the edge-aware flow smoothness term (0: the reference loss)")
     ap.add_argument("--edge-alpha", type=float, default=0.0,
                     help="edge sensitivity of the smoothness term (0: unweighted)")
+    ap.add_argument("--smoothness-order", type=int, default=1, choices=(1, 2),
+                    help="the smoothness term penalises the flow's first (1) or second (2) "
+                         "differences; 2 leaves an affine flow free")
     ap.add_argument("--census-weight", type=float, default=0.0,
                     help="weight of the soft ternary census data term (0: off)")
     ap.add_argument("--census-radius", type=int, default=3, choices=(1, 2, 3),
@@ -481,11 +484,14 @@ def header_record(args, augment=None):
     clip = args.clip_norm is not None or args.skip_nonfinite or args.log_grad_norm
     image = args.warp_convention == "image"
     occ = (args.occlusion != "none" or args.occ_alpha1 != 0.01 or args.occ_alpha2 != 0.5)
+    order2 = getattr(args, "smoothness_order", 1) == 2
     if not (args.smoothness_weight or args.edge_alpha or augment is not None or census or clip
-            or image or occ):
+            or image or occ or order2):
         return None
     head = {"header": True, "smoothness_weight": args.smoothness_weight,
             "edge_alpha": args.edge_alpha}
+    if order2:                      # first-order logs stay what they were
+        head["smoothness_order"] = 2
     if census:
         head.update(census_weight=args.census_weight, census_radius=args.census_radius,
                     photometric_weight=args.photometric_weight)
@@ -528,7 +534,8 @@ def main(argv=None):
                                photometric_weight=args.photometric_weight,
                                warp_convention=args.warp_convention,
                                occlusion=args.occlusion, occlusion_alpha1=args.occ_alpha1,
-                               occlusion_alpha2=args.occ_alpha2)
+                               occlusion_alpha2=args.occ_alpha2,
+                               smoothness_order=args.smoothness_order)
     except ValueError as e:
         ap.error(str(e))
     try:

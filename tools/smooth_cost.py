@@ -3,13 +3,15 @@
 python tools/smooth_cost.py [--rounds 20] [--warmup 3] [--out smooth_cost.json]
 
 Trainer.train_step at the bench size (384 x 512, B = 8, fp32, bench.py's initial weights and
-batch) in three arms that differ only in the loss layer: weight 0 (the reference loss), weight
-0.2 with edge_alpha 0, weight 0.2 with edge_alpha 10.  One net and one optimizer; the arms are
+batch) in five arms that differ only in the loss layer: weight 0 (the reference loss), weight
+0.2 with edge_alpha 0 and with edge_alpha 10, and the same two with the second-order term
+(smoothness_order=2).  One net and one optimizer; the arms are
 alternated step by step (so they see the same drifting state and the same neighbours on the
 machine), each step timed by a device event pair, after ``--warmup`` steps per arm.  Prints one
 JSON line: per arm the median, quartiles and minimum of the step time in ms.
 
-Kernel times (of_photo_l1_*_multi against of_flow_smooth_*_multi) come from a kernel trace of a
+Kernel times (of_photo_l1_*_multi against of_flow_smooth_*_multi and of_flow_smooth2_*_multi)
+come from a kernel trace of a
 short run of this script, a run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o cost -- \
         python tools/smooth_cost.py --rounds 5
@@ -25,7 +27,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ARMS = [("weight0", 0.0, 0.0), ("weight0.2_alpha0", 0.2, 0.0), ("weight0.2_alpha10", 0.2, 10.0)]
+# (name, smoothness_weight, edge_alpha, smoothness_order)
+ARMS = [("weight0", 0.0, 0.0, 1), ("weight0.2_alpha0", 0.2, 0.0, 1),
+        ("weight0.2_alpha10", 0.2, 10.0, 1), ("order2_weight0.2_alpha0", 0.2, 0.0, 2),
+        ("order2_weight0.2_alpha10", 0.2, 10.0, 2)]
 
 
 def main():
@@ -50,7 +55,7 @@ def main():
     net = FlowNet(H, W, values=init_params(flow_net_spec(levels=4), 0))
     trainer = Trainer(net, KerasAdam(net.store), LossLayer())
     batch = torch.from_numpy(synthetic_batch(B, H, W, seed=1234)).cuda()
-    layers = [LossLayer(w, a) for _, w, a in ARMS]
+    layers = [LossLayer(w, a, smoothness_order=o) for _, w, a, o in ARMS]
     times = [[] for _ in ARMS]
     step = 0
     for r in range(args.warmup + args.rounds):
@@ -65,12 +70,12 @@ def main():
                 times[k].append(e0.elapsed_time(e1))
             step += 1
     rec = {"size": [B, H, W], "rounds": args.rounds, "arms": {}}
-    for (name, w, a), t in zip(ARMS, times):
+    for (name, w, a, o), t in zip(ARMS, times):
         q = np.percentile(t, [25, 50, 75])
         rec["arms"][name] = {"median_ms": round(float(q[1]), 4), "q25_ms": round(float(q[0]), 4),
                              "q75_ms": round(float(q[2]), 4), "min_ms": round(float(min(t)), 4)}
     base = rec["arms"][ARMS[0][0]]["median_ms"]
-    for name, _, _ in ARMS[1:]:
+    for name, _, _, _ in ARMS[1:]:
         rec["arms"][name]["over_weight0_pct"] = round(
             100.0 * (rec["arms"][name]["median_ms"] / base - 1.0), 2)
     line = json.dumps(rec)
