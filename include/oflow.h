@@ -539,6 +539,43 @@ int of_census_fwd_multi_w(const float* const* img6s, const float* const* flows,
                           int levels, int radius, const float* coefs, float* const* workspaces,
                           float* const* dcdfs, float* partials, int convention, void* stream);
 
+/* Structural-similarity (SSIM) data term, 3 x 3 box windows, every level in one launch (levels
+ * <= 8; level l holds img6s[l] (n,hs[l],ws[l],6), of_pyramid6's output, and flows[l]
+ * (n,hs[l],ws[l],2), 8-byte aligned).  x is image 1 and y = warp(image 2, flow) in the given
+ * convention (the photometric and census terms' sampler, extrapolating outside the frame as it
+ * does there), both as intensities I[p,c] = img[p,c] + mean_c, mean = (123, 117, 104)/255 in
+ * stored channel order (the luminance factor is not shift-invariant).  Per channel c and per
+ * interior centre p (1 <= i <= h-2, 1 <= j <= w-2: "valid" windows, none crossing a row end or
+ * an image), with C1 = 0.01^2, C2 = 0.03^2:
+ *   mx, my      = 3x3 means of x, y around p
+ *   sx, sy, sxy = 3x3 means of (x-mx)^2, (y-my)^2, (x-mx)(y-my)      (centred sums)
+ *   S = (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sx + sy + C2)),   d[p,c] = (1 - S)/2
+ *   SSIM_l = sum_p m[p] sum_c d[p,c]        m = weights[l][p], the centre's weight (1 if none)
+ * S lies in [-1,1] for any reals, so d lies in [0,1] and no clamp is applied.  The kernel forms
+ * 1 - S = (1 - lum) + lum (1 - con) with 1 - lum = (mx-my)^2 / (mx^2+my^2+C1) and 1 - con =
+ * mean((x-mx - (y-my))^2) / (sx+sy+C2): the same number without the cancellation near S = 1.
+ * Forward: one partial per 8 x 32 pixel tile, concatenated in level order (of_ssim_partials
+ * gives a level's share); level l's slice sums to coefs[l] * SSIM_l and of_sum_partials reduces
+ * them.  A level with h or w < 3 has no window: its partials are 0.  When dsdfs is not NULL,
+ * dsdfs[l] (dense (n,hs[l],ws[l],2), 8-byte aligned) receives the unscaled d SSIM_l / d flow,
+ * every element written (zeros where no window reaches); the gradient is the closed form
+ *   d d_p / d y_q = (1/9) [P_p + Q_p (y_q - my_p) + R_p (x_q - mx_p)],
+ *   P = dd/dmy, Q = 2 dd/dsy, R = dd/dsxy,  box-summed over the interior centres that hold q.
+ * The images and the weights are constants; a NULL `weights`, or a NULL weights[l], is weight 1
+ * (bitwise what all-ones weights give).  of_ssim_bwd_multi scales the planes into d(flow): it
+ * is of_census_bwd_multi (same arguments, same kernel).  No atomics, no allocation, no host
+ * sync; run-to-run bitwise equal.  OF_EINVAL (and nothing launched or written) for levels
+ * outside 1..8, n, h or w < 1, an unknown convention, NULL img6s / flows / partials / hs / ws /
+ * coefs or a NULL entry of img6s / flows (or of dsdfs when given). */
+int of_ssim_partials(int n, int h, int w);
+int of_ssim_fwd_multi(const float* const* img6s, const float* const* flows,
+                      const float* const* weights, int n, const int* hs, const int* ws,
+                      int levels, const float* coefs, float* const* dsdfs, float* partials,
+                      int convention, void* stream);
+int of_ssim_bwd_multi(const float* const* dsdfs, int n, const int* hs, const int* ws,
+                      int levels, const float* coefs, const float* dloss,
+                      float* const* dflows, const int* lds, int accumulate, void* stream);
+
 /* Keras Adam (train.py:34,56; P13), one launch over a flat parameter arena, g' = g*gscale
  * (gscale folds the 1/world of a data-parallel gradient average):
  * m += (g'-m)(1-b1); v += (g'^2-v)(1-b2); p -= lr_t * m / (sqrt(v) + eps). */

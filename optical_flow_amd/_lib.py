@@ -220,6 +220,12 @@ PROTOTYPES = {
     "of_census_fwd_multi_w": (I, [C.POINTER(P), C.POINTER(P), C.POINTER(P), I, C.POINTER(I),
                                   C.POINTER(I), I, I, C.POINTER(F), C.POINTER(P), C.POINTER(P), P,
                                   I, P]),
+    # SSIM data term: weights and convention in the one forward; the backward is the census one
+    "of_ssim_partials": (I, [I, I, I]),
+    "of_ssim_fwd_multi": (I, [C.POINTER(P), C.POINTER(P), C.POINTER(P), I, C.POINTER(I),
+                              C.POINTER(I), I, C.POINTER(F), C.POINTER(P), P, I, P]),
+    "of_ssim_bwd_multi": (I, [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I, C.POINTER(F), P,
+                              C.POINTER(P), C.POINTER(I), I, P]),
     "of_stem_bwd_fused_workspace": (SZ, [PD, I]),
     "of_stem_bwd_fused": (I, [PD, I, P, I, P, P, P, P, P, P, F, P, P, P, P, I, P, SZ, P]),
     # BatchNormalization in training mode (bn_mode="training")

@@ -24,7 +24,14 @@ class LossLayer:
     an illumination-robust data term that compares the local intensity order of image 1 and
     of the warped image 2 in a (2 census_radius + 1)^2 window, averaged over pixels and scales
     (ops.census_loss; DESIGN.md "Census term").  ``photometric_weight`` scales the photometric
-    term; 0 drops it (its kernels are not launched), which needs ``census_weight`` > 0.
+    term; 0 drops it (its kernels are not launched), which needs another data term.
+
+    ``ssim_weight`` > 0 (build-added) adds that weight times the structural-similarity term:
+    the mean over scales, over the 3 x 3 windows that lie inside the image and over channels
+    of (1 - SSIM)/2 between image 1 and the warped image 2, on intensities (the channel means
+    added back), with C1 = 0.01^2, C2 = 0.03^2 and no clamp (ops.ssim_loss; DESIGN.md "SSIM
+    term").  The usual mix is ``photometric_weight=0.15, ssim_weight=0.85``.  The loss needs
+    at least one of the three data weights to be non-zero.
 
     ``warp_convention`` (build-added): "reference" (default) warps image 2 on the reference's
     transposed grid (P1); "image" takes the flows as image-coordinate displacements (channel 0
@@ -32,8 +39,8 @@ class LossLayer:
     brings the loss to zero.  It must be the net's (Trainer raises ValueError otherwise).
 
     ``occlusion`` (build-added, image convention only): "none" (default) scores every pixel;
-    "border" gives weight 0 in both data terms to the pixels whose sample point leaves the
-    frame (where the warp extrapolates); "fb" also to those that fail the forward-backward
+    "border" gives weight 0 in the data terms (SSIM: to the window centred there) to the
+    pixels whose sample point leaves the frame (where the warp extrapolates); "fb" also to those that fail the forward-backward
     consistency check |f + g~|^2 <= occlusion_alpha1 (|f|^2 + |g~|^2) + occlusion_alpha2
     (alpha2 in squared full-resolution pixels), and must be called with the doubled batch
     [pairs ; the same pairs with the two images exchanged] (Trainer.train_step forms it).  The
@@ -43,7 +50,7 @@ class LossLayer:
     def __init__(self, smoothness_weight=0.0, edge_alpha=0.0, smoothness_eps=1e-4,
                  census_weight=0.0, census_radius=3, photometric_weight=1.0,
                  warp_convention="reference", occlusion="none", occlusion_alpha1=0.01,
-                 occlusion_alpha2=0.5, smoothness_order=1):
+                 occlusion_alpha2=0.5, ssim_weight=0.0, smoothness_order=1):
         ops.warp_convention(warp_convention)
         self.warp_convention = warp_convention
         if occlusion not in ("none", "border", "fb"):
@@ -70,9 +77,11 @@ class LossLayer:
             raise ValueError("photometric_weight must be >= 0, got %r" % (photometric_weight,))
         if census_radius not in (1, 2, 3):
             raise ValueError("census_radius must be 1, 2 or 3, got %r" % (census_radius,))
-        if census_weight == 0 and photometric_weight == 0:
-            raise ValueError("census_weight and photometric_weight are both 0: the loss needs "
-                             "a data term")
+        if not ssim_weight >= 0:
+            raise ValueError("ssim_weight must be >= 0, got %r" % (ssim_weight,))
+        if census_weight == 0 and photometric_weight == 0 and ssim_weight == 0:
+            raise ValueError("census_weight, photometric_weight and ssim_weight are all 0: the "
+                             "loss needs a data term")
         if smoothness_order not in (1, 2) or isinstance(smoothness_order, bool):
             raise ValueError("smoothness_order must be 1 or 2, got %r" % (smoothness_order,))
         self.smoothness_order = int(smoothness_order)
@@ -82,6 +91,7 @@ class LossLayer:
         self.census_weight = float(census_weight)
         self.census_radius = int(census_radius)
         self.photometric_weight = float(photometric_weight)
+        self.ssim_weight = float(ssim_weight)
 
     def __call__(self, batch_imgs, flows):
         num_scales = len(flows)
@@ -94,6 +104,8 @@ class LossLayer:
         assert batch_imgs.shape[3] == 6
         # the first order is the ops entries' default: such a layer calls them as it always did
         order = {"smoothness_order": 2} if self.smoothness_order == 2 else {}
+        if self.ssim_weight != 0.0:     # without it the ops entries are called as before
+            order["ssim_weight"] = self.ssim_weight
         if self.occlusion != "none":
             if self.occlusion == "fb" and batch_imgs.shape[0] % 2:
                 raise ValueError("occlusion='fb' scores the doubled batch [pairs ; swapped "
@@ -107,7 +119,8 @@ class LossLayer:
                                         self.smoothness_weight, self.edge_alpha,
                                         self.smoothness_eps, self.warp_convention, weights=masks,
                                         **order)
-        if self.census_weight == 0.0 and self.photometric_weight == 1.0:
+        if self.census_weight == 0.0 and self.photometric_weight == 1.0 and \
+                self.ssim_weight == 0.0:
             if self.smoothness_weight == 0.0:
                 return ops.photometric_loss(batch_imgs, list(flows), self.warp_convention)
             return ops.flow_loss(batch_imgs, list(flows), self.smoothness_weight,

@@ -2111,9 +2111,9 @@ def halves(x):
 
 
 # ================================================================ photometric loss =====
-# The training loss: photometric, census and smoothness terms over one image pyramid, in one
-# autograd Function (_Loss, below).  Each term has a forward and a backward helper of the same
-# shape; ``lv`` is the list of (level, output, row stride) that _grad_targets builds.
+# The training loss: photometric, census, SSIM and smoothness terms over one image pyramid, in
+# one autograd Function (_Loss, below).  Each term has a forward and a backward helper of the
+# same shape; ``lv`` is the list of (level, output, row stride) that _grad_targets builds.
 def _arr(ctype, vals):
     return (ctype * len(vals))(*vals)
 
@@ -2295,6 +2295,49 @@ def _census_bwd(planes, lv, coefs, dloss, accumulate):
          _arr(C.c_int, [ld for _, _, ld in lv]), accumulate, _stream())
 
 
+# ==================================================================== SSIM term =====
+def _ssim_coefs(n, hs, ws, scale):
+    """The normalisers of the SSIM term, times ``scale``: the mean over each level's 3 x 3
+    windows and channels and over the levels; a level without a window contributes 0."""
+    ns = len(hs)
+    return [scale / (ns * n * (h - 2) * (w - 2) * 3) if h >= 3 and w >= 3 else 0.0
+            for h, w in zip(hs, ws)]
+
+
+def _ssim_fwd(pyr, fl, coefs, want_grad, wc=0, wts=None):
+    """of_ssim_fwd_multi over every level (the SSIM data term, include/oflow.h): (partials,
+    planes).  The partials sum to the weighted term (the coefficients are applied in the
+    kernel); planes[l] is the unscaled d SSIM_l / d flow, every element written, that
+    of_ssim_bwd_multi scales into d(flow), or None without want_grad.  ``wts``: per-level
+    pixel weights of the window centres, None for weight 1."""
+    lib = _lib.lib()
+    ns = len(fl)
+    n = fl[0].shape[0]
+    hs = [f.shape[1] for f in fl]
+    ws_ = [f.shape[2] for f in fl]
+    parts = torch.empty(sum(lib.of_ssim_partials(n, h, w) for h, w in zip(hs, ws_)),
+                        device=fl[0].device)
+    planes = [torch.empty_like(f) for f in fl] if want_grad else None
+    plp = _arr(C.c_void_p, [p.data_ptr() for p in planes]) if planes is not None else None
+    call("of_ssim_fwd_multi", _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
+         _arr(C.c_void_p, [f.data_ptr() for f in fl]),
+         _opt_ptrs(wts) if wts is not None else None, n, _arr(C.c_int, hs), _arr(C.c_int, ws_),
+         ns, _arr(C.c_float, coefs), plp, _ptr(parts), wc, _stream())
+    return parts, planes
+
+
+def _ssim_bwd(planes, lv, coefs, dloss, accumulate):
+    """of_ssim_bwd_multi for the levels in ``lv``."""
+    m = len(lv)
+    n = planes[0].shape[0]
+    call("of_ssim_bwd_multi", _arr(C.c_void_p, [planes[k].data_ptr() for k, _, _ in lv]), n,
+         _arr(C.c_int, [planes[k].shape[1] for k, _, _ in lv]),
+         _arr(C.c_int, [planes[k].shape[2] for k, _, _ in lv]), m,
+         _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
+         _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
+         _arr(C.c_int, [ld for _, _, ld in lv]), accumulate, _stream())
+
+
 # ============================================================ the loss Function =====
 def _flowgrads(flows):
     """Each flow's FlowGrad (None where a flow has none); if any of them does not have its
@@ -2341,42 +2384,43 @@ class _LossCfg(NamedTuple):
     wts: Optional[list] = None      # per-level pixel weights of the data terms ((n,h,w)
     #                                 tensors, constants: occlusion masks); None: unweighted
     fgs: Optional[list] = None      # per-level FlowGrad (_flowgrads); None: plain gradients
+    ssw: float = 0.0                # weight of the SSIM data term
 
 
 class _Loss(torch.autograd.Function):
-    """pw * photometric + cw * census + sw * smoothness, each the mean over the levels of
-    that level's mean, on one image pyramid; the images are constants.  A term whose weight
-    is 0 launches nothing, and the pyramid is only built when a term reads it (a data term,
-    or the smoothness term with edge_alpha != 0).  The smoothness term is never weighted by
-    ``wts``.
+    """pw * photometric + cw * census + ssw * SSIM + sw * smoothness, each the mean over the
+    levels of that level's mean, on one image pyramid; the images are constants.  A term whose
+    weight is 0 launches nothing, and the pyramid is only built when a term reads it (a data
+    term, or the smoothness term with edge_alpha != 0).  The smoothness term is never weighted
+    by ``wts``.
 
     One Function for all terms because of the FlowGrad protocol: the loss writes a flow's
     gradient buffer once and upscale_flow's backward adds to it afterwards, so two Functions
     returning gradients for the same flow would break it.  In the backward the terms run
-    photometric, census, smoothness; the first one present overwrites each level's d(flow)
-    output and the later ones add into it (``accumulate = 1``)."""
+    photometric, census, SSIM, smoothness; the first one present overwrites each level's
+    d(flow) output and the later ones add into it (``accumulate = 1``)."""
 
     @staticmethod
     def forward(ctx, batch_imgs, cfg, *flows):
-        pw, cw, sw = cfg.pw, cfg.cw, cfg.sw
+        pw, cw, sw, ssw = cfg.pw, cfg.cw, cfg.sw, cfg.ssw
         _check_dev(batch_imgs, *flows)
         ns = len(flows)
         assert 1 <= ns <= 8, "the loss kernels take 8 levels"
-        assert (ns if pw else 0) + (cw != 0) + (sw != 0) <= 8, \
-            "of_sum_partials takes 8 groups: one per photometric level, census, smoothness"
+        assert (ns if pw else 0) + (cw != 0) + (ssw != 0) + (sw != 0) <= 8, \
+            "of_sum_partials takes 8 groups: one per photometric level, census, SSIM, smoothness"
         fl = [f.contiguous() for f in flows]
         n = fl[0].shape[0]
         hs = [f.shape[1] for f in fl]
         ws_ = [f.shape[2] for f in fl]
         want_grad = any(ctx.needs_input_grad[2:])
         pyr = []
-        if pw != 0 or cw != 0 or cfg.edge_alpha != 0:
+        if pw != 0 or cw != 0 or ssw != 0 or cfg.edge_alpha != 0:
             pyr = _pyramid6(batch_imgs.contiguous(), fl)
         # The sum's groups are raw (pointer, count, coefficient): ``keep`` holds the partial
         # arrays until the sum is enqueued.  A dropped one's memory could be handed to the next
         # term's partials or to ``loss`` and be overwritten ahead of the sum on this stream.
         groups, keep = [], []
-        coefs = ccoefs = cv = ch = planes = None    # of the terms that are off
+        coefs = ccoefs = scoefs = cv = ch = planes = splanes = None    # of the terms that are off
         if pw != 0:
             coefs = [pw / (ns * n * h * w * 3) for h, w in zip(hs, ws_)]
             parts, nparts = _photo_fwd(pyr, fl, cfg.wts, cfg.wc)
@@ -2391,6 +2435,11 @@ class _Loss(torch.autograd.Function):
             cparts, planes = _census_fwd(pyr, fl, cfg.radius, ccoefs, want_grad, cfg.wc, cfg.wts)
             groups.append((cparts.data_ptr(), cparts.numel(), 1.0))
             keep.append(cparts)
+        if ssw != 0:
+            scoefs = _ssim_coefs(n, hs, ws_, ssw)
+            ssparts, splanes = _ssim_fwd(pyr, fl, scoefs, want_grad, cfg.wc, cfg.wts)
+            groups.append((ssparts.data_ptr(), ssparts.numel(), 1.0))
+            keep.append(ssparts)
         if sw != 0:
             cv, ch = _smooth_coefs(n, hs, ws_, sw, cfg.order)
             sparts = _smooth_fwd(pyr, fl, cfg.edge_alpha, cfg.eps, cv, ch, cfg.order)
@@ -2402,25 +2451,27 @@ class _Loss(torch.autograd.Function):
              len(groups), _ptr(loss), _stream())
         # Saved: only what a backward of a term that is on reads.  The pyramid: photometric,
         # and smoothness with edge_alpha != 0; the flows: photometric and smoothness; census
-        # alone keeps just its planes.
+        # and SSIM keep just their planes.
         keep_pyr = pyr if pw != 0 or (sw != 0 and cfg.edge_alpha != 0) else []
         keep_fl = fl if pw != 0 or sw != 0 else []
-        ctx.save_for_backward(*keep_pyr, *keep_fl, *(planes or []))
-        ctx.split = (len(keep_pyr), len(keep_pyr) + len(keep_fl))
+        ctx.save_for_backward(*keep_pyr, *keep_fl, *(planes or []), *(splanes or []))
+        ctx.split = (len(keep_pyr), len(keep_pyr) + len(keep_fl),
+                     len(keep_pyr) + len(keep_fl) + len(planes or []))
         ctx.wts = cfg.wts if pw != 0 else None      # the photometric backward reads them again
         ctx.cfg = cfg._replace(wts=None)
-        ctx.coefs = (coefs, ccoefs, cv, ch)
+        ctx.coefs = (coefs, ccoefs, cv, ch, scoefs)
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
         cfg = ctx.cfg
-        coefs, ccoefs, cv, ch = ctx.coefs
+        coefs, ccoefs, cv, ch, scoefs = ctx.coefs
         saved = ctx.saved_tensors
-        a, b = ctx.split
-        pyr, flows, planes = saved[:a], saved[a:b], saved[b:]
+        a, b, c = ctx.split
+        pyr, flows, planes, splanes = saved[:a], saved[a:b], saved[b:c], saved[c:]
         dloss = dloss.contiguous()
-        grads, lv = _grad_targets(cfg.fgs, flows or planes, ctx.needs_input_grad[2:])
+        grads, lv = _grad_targets(cfg.fgs, flows or planes or splanes,
+                                  ctx.needs_input_grad[2:])
         if lv:
             written = 0                # the first term present writes, the others add
             if cfg.pw != 0:
@@ -2428,6 +2479,9 @@ class _Loss(torch.autograd.Function):
                 written = 1
             if cfg.cw != 0:
                 _census_bwd(planes, lv, ccoefs, dloss, written)
+                written = 1
+            if cfg.ssw != 0:
+                _ssim_bwd(splanes, lv, scoefs, dloss, written)
                 written = 1
             if cfg.sw != 0:
                 _smooth_bwd(pyr, flows, lv, cfg.edge_alpha, cfg.eps, cv, ch, dloss, written,
@@ -2477,6 +2531,16 @@ def census_loss(batch_imgs, flows, radius=3, convention="reference"):
     return _Loss.apply(batch_imgs, cfg, *flows)
 
 
+def ssim_loss(batch_imgs, flows, convention="reference", weights=None):
+    """The SSIM term alone (a scalar; plain gradients for the flows): the mean over the
+    levels, the 3 x 3 windows inside the image and the channels of (1 - SSIM)/2 between image
+    1 and the warped image 2 (DESIGN.md "SSIM term").  ``weights``: as census_flow_loss's,
+    taken at each window's centre."""
+    wts = _pixel_weights(weights, flows) if weights is not None else None
+    cfg = _LossCfg(ssw=1.0, wc=warp_convention(convention), wts=wts)
+    return _Loss.apply(batch_imgs, cfg, *flows)
+
+
 def _pixel_weights(weights, flows):
     """census_flow_loss's ``weights`` as contiguous fp32 (n,h,w) tensors (None entries stay:
     weight 1 for that level)."""
@@ -2496,24 +2560,27 @@ def _pixel_weights(weights, flows):
 
 def census_flow_loss(batch_imgs, flows, census_weight, census_radius=3, photometric_weight=1.0,
                      smoothness_weight=0.0, edge_alpha=0.0, eps=1e-4, convention="reference",
-                     weights=None, smoothness_order=1):
+                     weights=None, ssim_weight=0.0, smoothness_order=1):
     """The training loss with the census data term: ``photometric_weight`` times
-    photometric_loss plus ``census_weight`` times census_loss plus ``smoothness_weight`` times
-    flow_smoothness (of ``smoothness_order`` 1 or 2), in one Function (see _Loss).  At least
-    one data weight must be
+    photometric_loss plus ``census_weight`` times census_loss plus ``ssim_weight`` times
+    ssim_loss plus ``smoothness_weight`` times flow_smoothness (of ``smoothness_order`` 1 or
+    2), in one Function (see _Loss).  At least one of the three data weights must be
     non-zero; the kernels of a term whose weight is 0 are not launched.
 
-    ``weights``: per level a (n,h,w) tensor of non-negative pixel weights for the two data
+    ``weights``: per level a (n,h,w) tensor of non-negative pixel weights for the data
     terms (occlusion_masks' output, or None for a level of weight 1).  They are constants; a
-    pixel's photometric error and its census window sum are multiplied by its weight, the
-    normalisers stay the means over all pixels, and the smoothness term is not weighted."""
+    pixel's photometric error, its census window sum and the SSIM error of the window centred
+    on it are multiplied by its weight, the normalisers stay the means over all pixels (all
+    windows), and the smoothness term is not weighted."""
     wts = _pixel_weights(weights, flows) if weights is not None else None
     cfg = _LossCfg(pw=float(photometric_weight), cw=float(census_weight),
                    radius=_census_radius(census_radius), sw=float(smoothness_weight),
                    edge_alpha=float(edge_alpha), eps=float(eps),
                    order=_smooth_order(smoothness_order),
-                   wc=warp_convention(convention), wts=wts, fgs=_flowgrads(flows))
-    assert cfg.pw != 0 or cfg.cw != 0, "a data term is needed: both data weights are 0"
+                   wc=warp_convention(convention), wts=wts, fgs=_flowgrads(flows),
+                   ssw=float(ssim_weight))
+    assert cfg.pw != 0 or cfg.cw != 0 or cfg.ssw != 0, \
+        "a data term is needed: all three data weights are 0"
     return _Loss.apply(batch_imgs, cfg, *flows)
 
 

@@ -402,6 +402,9 @@ def build_parser():
                     help="census window radius r, a (2r+1) x (2r+1) window")
     ap.add_argument("--photometric-weight", type=float, default=1.0,
                     help="weight of the photometric L1 term (0 with --census-weight: census only)")
+    ap.add_argument("--ssim-weight", type=float, default=0.0,
+                    help="weight of the 3x3 SSIM data term (0: off); the usual mix is "
+                         "--photometric-weight 0.15 --ssim-weight 0.85")
     ap.add_argument("--clip-norm", type=float, default=None, metavar="C",
                     help="clip the gradients to global L2 norm C (Keras global_clipnorm)")
     ap.add_argument("--skip-nonfinite", action="store_true",
@@ -485,13 +488,16 @@ def header_record(args, augment=None):
     image = args.warp_convention == "image"
     occ = (args.occlusion != "none" or args.occ_alpha1 != 0.01 or args.occ_alpha2 != 0.5)
     order2 = getattr(args, "smoothness_order", 1) == 2
+    ssim = getattr(args, "ssim_weight", 0.0)
     if not (args.smoothness_weight or args.edge_alpha or augment is not None or census or clip
-            or image or occ or order2):
+            or image or occ or order2 or ssim):
         return None
     head = {"header": True, "smoothness_weight": args.smoothness_weight,
             "edge_alpha": args.edge_alpha}
     if order2:                      # first-order logs stay what they were
         head["smoothness_order"] = 2
+    if ssim:                        # logs without the SSIM term stay what they were
+        head["ssim_weight"] = ssim
     if census:
         head.update(census_weight=args.census_weight, census_radius=args.census_radius,
                     photometric_weight=args.photometric_weight)
@@ -535,7 +541,8 @@ def main(argv=None):
                                warp_convention=args.warp_convention,
                                occlusion=args.occlusion, occlusion_alpha1=args.occ_alpha1,
                                occlusion_alpha2=args.occ_alpha2,
-                               smoothness_order=args.smoothness_order)
+                               smoothness_order=args.smoothness_order,
+                               ssim_weight=args.ssim_weight)
     except ValueError as e:
         ap.error(str(e))
     try:

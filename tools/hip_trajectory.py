@@ -3,6 +3,7 @@
 python tools/hip_trajectory.py --steps 26 [--det] [--precision fp32] --out gpurun_out/traj.jsonl
     [--smoothness-weight 0.2 --edge-alpha 10]      (the loss with the smoothness term on)
     [--census-weight 1 --census-radius 3 --photometric-weight 1]    (with the census term on)
+    [--photometric-weight 0.15 --ssim-weight 0.85]                  (with the SSIM term on)
     [--clip-norm C] [--skip-nonfinite] [--track-grad-norm]   (KerasAdam's global_clipnorm, the
         non-finite guard, the norm alone; each adds grad_norm and skipped to every record)
 
@@ -39,6 +40,7 @@ def main():
     ap.add_argument("--census-weight", type=float, default=0.0)
     ap.add_argument("--census-radius", type=int, default=3)
     ap.add_argument("--photometric-weight", type=float, default=1.0)
+    ap.add_argument("--ssim-weight", type=float, default=0.0)
     ap.add_argument("--clip-norm", type=float, default=None)
     ap.add_argument("--skip-nonfinite", action="store_true")
     ap.add_argument("--track-grad-norm", action="store_true")
@@ -62,7 +64,8 @@ def main():
                       LossLayer(args.smoothness_weight, args.edge_alpha,
                                 census_weight=args.census_weight,
                                 census_radius=args.census_radius,
-                                photometric_weight=args.photometric_weight))
+                                photometric_weight=args.photometric_weight,
+                                ssim_weight=args.ssim_weight))
     batch_np = synthetic_batch(B, H, W, seed=1234)
     batch = torch.from_numpy(batch_np).cuda()
     blocks = list(encoder_blocks(4))
@@ -75,6 +78,9 @@ def main():
             if args.census_weight or args.photometric_weight != 1.0:
                 rec.update({"census_weight": args.census_weight,
                             "census_radius": args.census_radius,
+                            "photometric_weight": args.photometric_weight})
+            if args.ssim_weight:
+                rec.update({"ssim_weight": args.ssim_weight,
                             "photometric_weight": args.photometric_weight})
             if args.oracle_every and s % args.oracle_every == 0:
                 from oracle import ref_flow as R

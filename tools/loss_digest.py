@@ -1,6 +1,6 @@
 """Digests of every loss entry's outputs, for a bitwise A/B of two trees (GPU).
 
-python tools/loss_digest.py [--out loss_digest.txt]
+python tools/loss_digest.py [--ssim] [--out loss_digest.txt]
 
 Seeded inputs at the bench's loss size (384 x 512, B = 8, four levels of flows, scale 2).  For
 every public loss entry of optical_flow_amd.ops and every combination of terms that takes a
@@ -45,6 +45,17 @@ ROWS = [
     ("census_flow_loss(three terms, weights=ones)",
      lambda o, b, f, **c: _three(o, b, f, weights=_ones(f), **c), True),
 ]
+# the rows of the SSIM term (--ssim; a tree without the term has none of them)
+SSIM_ROWS = [
+    ("ssim_loss", lambda o, b, f, **c: o.ssim_loss(b, f, **c), True),
+    ("census_flow_loss(0.15 L1 + 0.85 SSIM)",
+     lambda o, b, f, **c: o.census_flow_loss(b, f, 0.0, photometric_weight=0.15,
+                                             ssim_weight=0.85, **c), True),
+    ("census_flow_loss(four terms)", lambda o, b, f, **c: _three(o, b, f, ssim_weight=0.7, **c),
+     True),
+    ("census_flow_loss(four terms, weights=ones)",
+     lambda o, b, f, **c: _three(o, b, f, ssim_weight=0.7, weights=_ones(f), **c), True),
+]
 
 
 def _sha(t):
@@ -54,6 +65,8 @@ def _sha(t):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ssim", action="store_true",
+                    help="append the rows of the SSIM term (the other rows stay what they are)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("loss_digest.py runs the loss kernels; no GPU is visible")
@@ -65,7 +78,7 @@ def main():
     flows = [torch.tensor(rng.standard_normal((B, H >> (s + 1), W >> (s + 1), 2)) * 2.0,
                           dtype=torch.float32).cuda() for s in range(LEVELS)]
     lines = []
-    for row, fn, has_convention in ROWS:
+    for row, fn, has_convention in ROWS + (SSIM_ROWS if args.ssim else []):
         for conv in (("reference", "image") if has_convention else ("-",)):
             fd = [f.clone().requires_grad_(True) for f in flows]
             loss = fn(ops, batch, fd, **({"convention": conv} if has_convention else {}))
