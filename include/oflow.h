@@ -931,6 +931,48 @@ int of_flow_eval(const float* flow, int n, int fh, int fw, const void* dev_gt_ra
 int of_flow_upsample(const float* flow, int n, int fh, int fw, int gh, int gw, float* out,
                      void* stream);
 
+/* Supervised term of the training loss (build-added): the Charbonnier end-point error of every
+ * level's flow against KITTI ground truth, all levels in one launch (levels <= 8), image
+ * convention only.  flows[l]: (n, fhs[l], fws[l], 2) fp32, 8-byte aligned, in pixels of its own
+ * grid.  dev_gt_raw / host_descs / gt_bytes: of_flow_eval's ground-truth batch, holding n_gt
+ * maps (1 <= n_gt <= n); images n_gt .. n-1 of the flows have no ground truth and contribute
+ * nothing (the swapped half of a forward-backward batch).  For a valid pixel p (B != 0) of image
+ * i, with u_l(p) exactly of_flow_eval's sampled and scaled flow of level l (the same __device__
+ * sampler) and gt(p) its decode:
+ *   e = u_l(p) - gt(p);   rho(e) = (e_x^2 + e_y^2 + eps^2)^(q/2)      (fp32; q == 1: sqrtf,
+ *                                                    else exp2(q/2 * log2(.)))
+ *   S_l,i = mean of rho over the valid pixels of image i
+ *   S_l   = mean of S_l,i over the images with a valid pixel (0 when there is none)
+ * Errors are in native pixels at every level.  A counting pass (integers) leaves the per-image
+ * weight w_i = 1 / (n_nonempty * n_valid_i), 0 for an empty image, in `workspace`; nothing is
+ * read back.  Forward: level l's slice of `partials` (of_supervised_partials(n, fhs[l], fws[l],
+ * max_gh, max_gw) floats, in level order) sums to coefs[l] * S_l and of_sum_partials reduces
+ * them.  When dsdfs is not NULL, dsdfs[l] (dense (n, fhs[l], fws[l], 2), 8-byte aligned)
+ * receives d(coefs[l] * S_l) / d flows[l], every element written (zeros for cells no valid
+ * pixel touches, for empty images and for images without ground truth):
+ *   d / d cell c = coefs[l] w_i (ku, kv) sum_p wt_c(p) q (|e|^2 + eps^2)^(q/2 - 1) e,
+ * wt_c(p) the cell's bilinear weight in u_l(p) (both taps of an axis when the border clamps
+ * them onto one cell), (ku, kv) = (gw / fw, gh / fh).  Gather form: a cell sums the native pixels
+ * whose footprint touches it, per lane in index order in double, then a shuffle tree and, for
+ * a large footprint, the workgroup's waves in wave order.  No atomics, no allocation, no host
+ * sync; run-to-run bitwise equal.  of_census_bwd_multi (coefs 1) scales the planes into d(flow).
+ * max_gh / max_gw bound every map of the batch: they size the counting grid and decide how
+ * many waves share a cell (a larger map is still summed whole).  workspace: 16-byte aligned,
+ * of_supervised_workspace_bytes(n, max_gh, max_gw) bytes.
+ * OF_EINVAL (and no launch) for levels outside 1..8, n outside 1..65535, n_gt outside 1..n, a
+ * grid size < 1, q outside (0, 2], eps <= 0, max_gh or max_gw < 1, a NULL flows / fhs / fws /
+ * coefs / dev_gt_raw / workspace / partials or a NULL or misaligned entry of flows (or of dsdfs
+ * when given), dev_gt_raw or workspace not 16-byte aligned, a workspace that is too small, a bad
+ * host descriptor (as of_flow_eval checks them). */
+int of_supervised_partials(int n, int fh, int fw, int max_gh, int max_gw);
+int64_t of_supervised_workspace_bytes(int n, int max_gh, int max_gw);
+int of_supervised_fwd_multi(const float* const* flows, int n, int n_gt, const int* fhs,
+                            const int* fws, int levels, const void* dev_gt_raw,
+                            const of_image_desc* host_descs, int64_t gt_bytes, int max_gh,
+                            int max_gw, float q, float eps, const float* coefs, void* workspace,
+                            int64_t workspace_bytes, float* const* dsdfs, float* partials,
+                            void* stream);
+
 /* ==== SURVEY.md §8 f row 2: TensorFlow checkpoint bundles (save_weights / load_weights) ===== */
 
 /* CRC32C (Castagnoli) of n bytes, continuing from crc (0 to start; unmasked).  The bundle's

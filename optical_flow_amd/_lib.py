@@ -226,6 +226,11 @@ PROTOTYPES = {
                               C.POINTER(I), I, C.POINTER(F), C.POINTER(P), P, I, P]),
     "of_ssim_bwd_multi": (I, [C.POINTER(P), I, C.POINTER(I), C.POINTER(I), I, C.POINTER(F), P,
                               C.POINTER(P), C.POINTER(I), I, P]),
+    # supervised term: of_flow_eval's ground-truth arguments; the backward is the census one
+    "of_supervised_partials": (I, [I, I, I, I, I]),
+    "of_supervised_workspace_bytes": (I64, [I, I, I]),
+    "of_supervised_fwd_multi": (I, [C.POINTER(P), I, I, C.POINTER(I), C.POINTER(I), I, P, P, I64,
+                                    I, I, F, F, C.POINTER(F), P, I64, C.POINTER(P), P, P]),
     "of_stem_bwd_fused_workspace": (SZ, [PD, I]),
     "of_stem_bwd_fused": (I, [PD, I, P, I, P, P, P, P, P, P, F, P, P, P, P, I, P, SZ, P]),
     # BatchNormalization in training mode (bn_mode="training")

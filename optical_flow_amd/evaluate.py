@@ -31,9 +31,8 @@ import torch
 
 from ._lib import call, lib
 
-# of_image_desc (include/oflow.h)
-DESC_DTYPE = np.dtype([("offset", np.int64), ("h", np.int32), ("w", np.int32)])
-assert DESC_DTYPE.itemsize == 16
+# the raw ground-truth batch (shared with the supervised loss term)
+from .gt_raw import DESC_DTYPE, _upload, device_gt, pack_gt_raw  # noqa: F401
 
 
 # ---- KITTI flow files -------------------------------------------------------------------------
@@ -111,37 +110,99 @@ def list_kitti_flow(root: str, gt: str = "occ"):
     return frames
 
 
+def split_kitti_flow(frames, holdout_every: int):
+    """(train, val) of list_kitti_flow's list: ``val`` is every ``holdout_every``-th frame of
+    the sorted list (indices holdout_every - 1, 2 * holdout_every - 1, ...), ``train`` the
+    rest, both in sorted order."""
+    if isinstance(holdout_every, bool) or int(holdout_every) != holdout_every or holdout_every < 2:
+        raise ValueError("holdout_every must be an integer >= 2, got %r" % (holdout_every,))
+    frames = sorted(tuple(f) for f in frames)
+    k = int(holdout_every)
+    val = [f for i, f in enumerate(frames) if (i + 1) % k == 0]
+    train = [f for i, f in enumerate(frames) if (i + 1) % k != 0]
+    return train, val
+
+
+class KittiFlowReader:
+    """Labelled batches of a KITTI 2015 flow tree for supervised fine-tuning: iterating yields
+    ``(batch, gt_raw, descs)`` -- the (B, H, W, 6) CUDA batch of_preprocess_pairs makes of the
+    frames, and pack_gt_raw's ground-truth buffer (on the GPU) with its host descriptors, which
+    Trainer.train_step takes as ``gt=(gt_raw, descs)``.
+
+    Every iteration is one epoch: the frames in a seeded shuffle of their own (``order``), the
+    last short batch dropped.  Frames and maps are decoded ``nworkers`` at a time, up to two
+    batches ahead, as evaluate() does; both go up by asynchronous copies from pinned staging.
+    No spatial augmentation: it would have to move the ground truth with the frame, so an
+    ``augment`` other than None raises ValueError."""
+
+    def __init__(self, frames_or_root, batch_size: int, img_height: int, img_width: int,
+                 gt: str = "occ", nworkers: int = 6, seed: int = 0, augment=None):
+        if augment is not None:
+            raise ValueError("labelled KITTI flow frames are not augmented (AugmentOpts given): a "
+                             "crop, zoom or flip would have to move the ground truth with it")
+        if isinstance(frames_or_root, (str, os.PathLike)):
+            frames = list_kitti_flow(frames_or_root, gt)
+        else:
+            frames = [tuple(f) for f in frames_or_root]
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1, got %r" % (batch_size,))
+        if len(frames) < batch_size:
+            raise ValueError("%d labelled frames do not fill one batch of %d"
+                             % (len(frames), batch_size))
+        self.frames = frames
+        self.batch_size = int(batch_size)
+        self.height, self.width = int(img_height), int(img_width)
+        self.nworkers = max(1, int(nworkers))
+        self.seed = int(seed)
+        self.nbatches = len(frames) // self.batch_size
+        self.epoch = 0
+
+    def order(self, epoch: int):
+        """The frame indices of ``epoch`` in reading order: a permutation seeded by (seed,
+        epoch), cut to whole batches."""
+        perm = np.random.default_rng([self.seed, int(epoch)]).permutation(len(self.frames))
+        return [int(i) for i in perm[:self.nbatches * self.batch_size]]
+
+    def host_batches(self, epoch: int):
+        """The epoch's batches on the host: (pairs, maps, indices) per batch -- BGR uint8 frame
+        pairs, (h, w, 3) uint16 maps, the frames' indices.  No GPU work."""
+        order = self.order(epoch)
+        pending = collections.deque()
+        todo = iter(order)
+        with cf.ThreadPoolExecutor(self.nworkers) as pool:
+            def fill():
+                while len(pending) < 2 * self.batch_size:
+                    i = next(todo, None)
+                    if i is None:
+                        return
+                    pending.append((i, pool.submit(_decode_frame, self.frames[i])))
+            fill()
+            while pending:
+                pairs, maps, idx = [], [], []
+                while len(pairs) < self.batch_size:
+                    i, fut = pending.popleft()
+                    (img1, img2, gmap), _ = fut.result()
+                    pairs.append((img1, img2))
+                    maps.append(gmap)
+                    idx.append(i)
+                    fill()
+                yield pairs, maps, idx
+
+    def __iter__(self):
+        from .data_reader import _pack_raw
+        epoch, self.epoch = self.epoch, self.epoch + 1
+        for pairs, maps, _ in self.host_batches(epoch):
+            dev = _upload(_pack_raw(pairs))
+            batch = torch.empty((len(pairs), self.height, self.width, 6), device="cuda")
+            call("of_preprocess_pairs", C.c_void_p(dev.data_ptr()), len(pairs), self.height,
+                 self.width, C.c_void_p(batch.data_ptr()), _stream())
+            raw, descs = pack_gt_raw(maps)
+            yield batch, _upload(raw), descs
+
+
 # ---- device ops -------------------------------------------------------------------------------
-def pack_gt_raw(maps):
-    """[(h_i, w_i, 3) uint16, ...] -> (raw uint8 buffer, descriptors): of_image_desc[n] padded to
-    256 bytes, then the maps, each at a 256-byte aligned offset (the raw image batch's layout)."""
-    n = len(maps)
-    total = -(-16 * n // 256) * 256
-    desc = np.zeros(n, DESC_DTYPE)
-    for i, m in enumerate(maps):
-        if m.dtype != np.uint16 or m.ndim != 3 or m.shape[2] != 3:
-            raise ValueError("ground-truth map %d must be (h, w, 3) uint16, got %s %r" %
-                             (i, m.dtype, m.shape))
-        desc[i] = (total, m.shape[0], m.shape[1])
-        total += -(-m.nbytes // 256) * 256
-    raw = np.zeros(max(total, 256), np.uint8)
-    raw[:16 * n] = desc.view(np.uint8)
-    for d, m in zip(desc, maps):
-        raw[d["offset"]:d["offset"] + m.nbytes] = np.ascontiguousarray(m).reshape(-1).view(np.uint8)
-    return raw, desc
-
-
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _upload(host: np.ndarray) -> torch.Tensor:
-    """A host byte buffer to the GPU without a host wait: staged in pinned memory (torch's host
-    allocator keeps a block until the copy that reads it has completed), copied non_blocking on
-    the current stream."""
-    staged = torch.empty(host.size, dtype=torch.uint8, pin_memory=True)
-    staged.numpy()[:] = host.reshape(-1)
-    return staged.cuda(non_blocking=True)
 
 
 def _flow_arg(flow):
@@ -159,19 +220,7 @@ def flow_metrics(flow: torch.Tensor, gt_raw, descs=None):
     read back."""
     flow = _flow_arg(flow)
     n, fh, fw = flow.shape[:3]
-    if isinstance(gt_raw, (list, tuple)):
-        gt_raw, descs = pack_gt_raw(gt_raw)
-    if isinstance(gt_raw, np.ndarray):
-        if descs is None:
-            descs = gt_raw[:16 * n].view(DESC_DTYPE).copy()
-        gt_raw = _upload(gt_raw)
-    if descs is None:
-        raise ValueError("a device ground-truth buffer needs its host descriptors")
-    descs = np.ascontiguousarray(descs, dtype=DESC_DTYPE)
-    if not (torch.is_tensor(gt_raw) and gt_raw.is_cuda and gt_raw.dtype == torch.uint8):
-        raise ValueError("the ground-truth buffer must be a CUDA uint8 tensor")
-    if len(descs) != n:
-        raise ValueError("%d descriptors for %d flows" % (len(descs), n))
+    gt_raw, descs = device_gt(gt_raw, descs, n)
     npart = lib().of_flow_eval_partials(n, int(descs["h"].max(initial=1)),
                                         int(descs["w"].max(initial=1)))
     partials = torch.empty(max(3 * npart, 1), dtype=torch.float64, device="cuda")

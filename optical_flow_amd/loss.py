@@ -45,12 +45,26 @@ class LossLayer:
     (alpha2 in squared full-resolution pixels), and must be called with the doubled batch
     [pairs ; the same pairs with the two images exchanged] (Trainer.train_step forms it).  The
     masks are computed from the flows as constants (ops.occlusion_masks; DESIGN.md "Occlusion
-    masks"); the means stay over all pixels and the smoothness term is not masked."""
+    masks"); the means stay over all pixels and the smoothness term is not masked.
+
+    ``supervised_weight`` > 0 (build-added, image convention only) adds that weight times the
+    supervised term against KITTI flow ground truth, passed to the call as ``gt`` (a list of
+    (h, w, 3) uint16 maps, pack_gt_raw's buffer, or (buffer, descriptors)): per scale the
+    flow is upsampled to each map's native size as the evaluation samples it, and the
+    Charbonnier end-point error (|u - gt|^2 + supervised_eps^2)^(supervised_q / 2), in native
+    pixels, is averaged over an image's valid pixels, then over the images that have one, then
+    over the scales with ``supervised_level_weights`` (default 1 / scales each)
+    (ops.supervised_flow_loss; DESIGN.md "Supervised term").  With it the three unsupervised
+    data weights may all be 0 (pure fine-tuning).  With ``occlusion="fb"`` it scores the
+    forward pairs only (the first half of the doubled batch); the occlusion masks do not weigh
+    it."""
 
     def __init__(self, smoothness_weight=0.0, edge_alpha=0.0, smoothness_eps=1e-4,
                  census_weight=0.0, census_radius=3, photometric_weight=1.0,
                  warp_convention="reference", occlusion="none", occlusion_alpha1=0.01,
-                 occlusion_alpha2=0.5, ssim_weight=0.0, smoothness_order=1):
+                 occlusion_alpha2=0.5, ssim_weight=0.0, supervised_weight=0.0,
+                 supervised_q=1.0, supervised_eps=0.01, supervised_level_weights=None,
+                 smoothness_order=1):
         ops.warp_convention(warp_convention)
         self.warp_convention = warp_convention
         if occlusion not in ("none", "border", "fb"):
@@ -79,7 +93,27 @@ class LossLayer:
             raise ValueError("census_radius must be 1, 2 or 3, got %r" % (census_radius,))
         if not ssim_weight >= 0:
             raise ValueError("ssim_weight must be >= 0, got %r" % (ssim_weight,))
-        if census_weight == 0 and photometric_weight == 0 and ssim_weight == 0:
+        if not supervised_weight >= 0:
+            raise ValueError("supervised_weight must be >= 0, got %r" % (supervised_weight,))
+        if not 0 < supervised_q <= 2:
+            raise ValueError("supervised_q must be in (0, 2], got %r" % (supervised_q,))
+        if not supervised_eps > 0:
+            raise ValueError("supervised_eps must be > 0, got %r" % (supervised_eps,))
+        if supervised_level_weights is not None:
+            supervised_level_weights = tuple(float(v) for v in supervised_level_weights)
+            if not supervised_level_weights or not all(v >= 0 for v in supervised_level_weights):
+                raise ValueError("supervised_level_weights must be a non-empty sequence of "
+                                 "values >= 0, got %r" % (supervised_level_weights,))
+        if supervised_weight > 0 and warp_convention != "image":
+            raise ValueError("supervised_weight > 0 needs warp_convention='image': a "
+                             "%r-convention flow is not a displacement, its error against "
+                             "ground truth means nothing" % (warp_convention,))
+        self.supervised_weight = float(supervised_weight)
+        self.supervised_q = float(supervised_q)
+        self.supervised_eps = float(supervised_eps)
+        self.supervised_level_weights = supervised_level_weights
+        if census_weight == 0 and photometric_weight == 0 and ssim_weight == 0 and \
+                supervised_weight == 0:
             raise ValueError("census_weight, photometric_weight and ssim_weight are all 0: the "
                              "loss needs a data term")
         if smoothness_order not in (1, 2) or isinstance(smoothness_order, bool):
@@ -93,7 +127,11 @@ class LossLayer:
         self.photometric_weight = float(photometric_weight)
         self.ssim_weight = float(ssim_weight)
 
-    def __call__(self, batch_imgs, flows):
+    def __call__(self, batch_imgs, flows, gt=None):
+        if self.supervised_weight > 0 and gt is None:
+            raise ValueError("supervised_weight > 0: the call needs the ground truth (gt)")
+        if self.supervised_weight == 0 and gt is not None:
+            raise ValueError("ground truth given, but supervised_weight is 0")
         num_scales = len(flows)
         H, W = batch_imgs.shape[1], batch_imgs.shape[2]
         for scale_idx in range(num_scales):
@@ -106,6 +144,20 @@ class LossLayer:
         order = {"smoothness_order": 2} if self.smoothness_order == 2 else {}
         if self.ssim_weight != 0.0:     # without it the ops entries are called as before
             order["ssim_weight"] = self.ssim_weight
+        if self.supervised_weight != 0.0:
+            if self.supervised_level_weights is not None and \
+                    len(self.supervised_level_weights) != num_scales:
+                raise ValueError("supervised_level_weights has %d values for %d flows"
+                                 % (len(self.supervised_level_weights), num_scales))
+            order.update(supervised_weight=self.supervised_weight,
+                         supervised_q=self.supervised_q, supervised_eps=self.supervised_eps,
+                         supervised_level_weights=self.supervised_level_weights,
+                         gt=self._forward_gt(gt, batch_imgs.shape[0]))
+            if self.occlusion == "none":
+                return ops.census_flow_loss(batch_imgs, list(flows), self.census_weight,
+                                            self.census_radius, self.photometric_weight,
+                                            self.smoothness_weight, self.edge_alpha,
+                                            self.smoothness_eps, self.warp_convention, **order)
         if self.occlusion != "none":
             if self.occlusion == "fb" and batch_imgs.shape[0] % 2:
                 raise ValueError("occlusion='fb' scores the doubled batch [pairs ; swapped "
@@ -130,3 +182,9 @@ class LossLayer:
                                     self.census_radius, self.photometric_weight,
                                     self.smoothness_weight, self.edge_alpha,
                                     self.smoothness_eps, self.warp_convention, **order)
+
+    def _forward_gt(self, gt, nb):
+        """The ground truth as ops takes it; with occlusion="fb" it belongs to the forward
+        pairs, the first half of the doubled batch."""
+        n = nb // 2 if self.occlusion == "fb" else nb
+        return ops._gt_handle(gt, n)

@@ -2338,6 +2338,73 @@ def _ssim_bwd(planes, lv, coefs, dloss, accumulate):
          _arr(C.c_int, [ld for _, _, ld in lv]), accumulate, _stream())
 
 
+# ============================================================== supervised term =====
+def _gt_handle(gt, n):
+    """The ground truth of a supervised term as (CUDA uint8 buffer, host descriptors): ``gt`` is
+    a list of (h, w, 3) uint16 maps, pack_gt_raw's buffer (numpy or CUDA; ``n`` images unless
+    the descriptors say otherwise), or the pair (buffer, descriptors)."""
+    import numpy as np
+    from .gt_raw import device_gt
+    descs = None
+    if isinstance(gt, (list, tuple)) and len(gt) == 2 and \
+            getattr(gt[0], "dtype", None) in (np.uint8, torch.uint8):
+        gt, descs = gt
+    if isinstance(gt, (list, tuple)):
+        n = len(gt)
+    elif descs is not None:
+        n = len(descs)
+    return device_gt(gt, descs, n)
+
+
+def _sup_level_weights(level_weights, ns):
+    """The supervised term's per-level weights: 1 / levels each by default, else the caller's,
+    used as given."""
+    if level_weights is None:
+        return (1.0 / ns,) * ns
+    lw = tuple(float(v) for v in level_weights)
+    if len(lw) != ns:
+        raise ValueError("supervised level weights: %d values for %d flows" % (len(lw), ns))
+    if not all(v >= 0 for v in lw):
+        raise ValueError("supervised level weights must be >= 0, got %r" % (lw,))
+    return lw
+
+
+def _sup_fwd(fl, gt, q, eps, coefs, want_grad):
+    """of_supervised_fwd_multi over every level (the supervised term, include/oflow.h):
+    (partials, per-level counts, planes).  Level l's slice of the partials sums to coefs[l] *
+    S_l (the coefficients are applied in the kernel); planes[l] is d(coefs[l] * S_l) / d flow,
+    every element written, that the pixelwise plane scaling (of_census_bwd_multi) turns into
+    d(flow), or None without want_grad.  ``gt``: (CUDA buffer, host descriptors) of the first
+    len(descriptors) images; the others have no ground truth."""
+    lib = _lib.lib()
+    ns = len(fl)
+    n = fl[0].shape[0]
+    raw, descs = gt
+    n_gt = len(descs)
+    if not 1 <= n_gt <= n:
+        raise ValueError("ground truth for %d images, flows for %d" % (n_gt, n))
+    hs = [f.shape[1] for f in fl]
+    ws_ = [f.shape[2] for f in fl]
+    mh, mw = int(descs["h"].max(initial=1)), int(descs["w"].max(initial=1))
+    nparts = [lib.of_supervised_partials(n, h, w, mh, mw) for h, w in zip(hs, ws_)]
+    parts = torch.empty(sum(nparts), device=fl[0].device)
+    planes = [torch.empty_like(f) for f in fl] if want_grad else None
+    plp = _arr(C.c_void_p, [p.data_ptr() for p in planes]) if planes is not None else None
+    wsb = lib.of_supervised_workspace_bytes(n, mh, mw)
+    wsk, wsp, _ = _workspace(wsb, fl[0].device)
+    call("of_supervised_fwd_multi", _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, n_gt,
+         _arr(C.c_int, hs), _arr(C.c_int, ws_), ns, _ptr(raw),
+         descs.ctypes.data_as(C.c_void_p), raw.numel(), mh, mw, q, eps, _arr(C.c_float, coefs),
+         wsp, wsb, plp, _ptr(parts), _stream())
+    return parts, nparts, planes
+
+
+def _sup_bwd(planes, lv, dloss, accumulate):
+    """The supervised planes scaled by dloss into d(flow): of_census_bwd_multi with unit
+    coefficients (the planes carry theirs)."""
+    _census_bwd(planes, lv, [1.0] * len(planes), dloss, accumulate)
+
+
 # ============================================================ the loss Function =====
 def _flowgrads(flows):
     """Each flow's FlowGrad (None where a flow has none); if any of them does not have its
@@ -2385,11 +2452,17 @@ class _LossCfg(NamedTuple):
     #                                 tensors, constants: occlusion masks); None: unweighted
     fgs: Optional[list] = None      # per-level FlowGrad (_flowgrads); None: plain gradients
     ssw: float = 0.0                # weight of the SSIM data term
+    supw: float = 0.0               # supervised term: its weight, the penalty's exponent and
+    supq: float = 1.0               # eps, the per-level weights (None: 1 / levels) and the
+    supeps: float = 0.01            # ground truth as _gt_handle gives it
+    suplw: Optional[tuple] = None
+    gt: Optional[tuple] = None
 
 
 class _Loss(torch.autograd.Function):
-    """pw * photometric + cw * census + ssw * SSIM + sw * smoothness, each the mean over the
-    levels of that level's mean, on one image pyramid; the images are constants.  A term whose
+    """pw * photometric + cw * census + ssw * SSIM + supw * supervised + sw * smoothness, each
+    the mean over the levels of that level's mean (the supervised term: its own level weights,
+    against the ground truth ``cfg.gt``), on one image pyramid; the images are constants.  A term whose
     weight is 0 launches nothing, and the pyramid is only built when a term reads it (a data
     term, or the smoothness term with edge_alpha != 0).  The smoothness term is never weighted
     by ``wts``.
@@ -2397,7 +2470,7 @@ class _Loss(torch.autograd.Function):
     One Function for all terms because of the FlowGrad protocol: the loss writes a flow's
     gradient buffer once and upscale_flow's backward adds to it afterwards, so two Functions
     returning gradients for the same flow would break it.  In the backward the terms run
-    photometric, census, SSIM, smoothness; the first one present overwrites each level's
+    photometric, census, SSIM, supervised, smoothness; the first one present overwrites each level's
     d(flow) output and the later ones add into it (``accumulate = 1``)."""
 
     @staticmethod
@@ -2406,8 +2479,10 @@ class _Loss(torch.autograd.Function):
         _check_dev(batch_imgs, *flows)
         ns = len(flows)
         assert 1 <= ns <= 8, "the loss kernels take 8 levels"
-        assert (ns if pw else 0) + (cw != 0) + (ssw != 0) + (sw != 0) <= 8, \
-            "of_sum_partials takes 8 groups: one per photometric level, census, SSIM, smoothness"
+        supw = cfg.supw
+        assert (ns if pw else 0) + (cw != 0) + (ssw != 0) + (sw != 0) + (supw != 0) <= 8, \
+            "of_sum_partials takes 8 groups: one per photometric level, census, SSIM, " \
+            "supervised, smoothness"
         fl = [f.contiguous() for f in flows]
         n = fl[0].shape[0]
         hs = [f.shape[1] for f in fl]
@@ -2421,6 +2496,7 @@ class _Loss(torch.autograd.Function):
         # term's partials or to ``loss`` and be overwritten ahead of the sum on this stream.
         groups, keep = [], []
         coefs = ccoefs = scoefs = cv = ch = planes = splanes = None    # of the terms that are off
+        supplanes = None
         if pw != 0:
             coefs = [pw / (ns * n * h * w * 3) for h, w in zip(hs, ws_)]
             parts, nparts = _photo_fwd(pyr, fl, cfg.wts, cfg.wc)
@@ -2440,6 +2516,12 @@ class _Loss(torch.autograd.Function):
             ssparts, splanes = _ssim_fwd(pyr, fl, scoefs, want_grad, cfg.wc, cfg.wts)
             groups.append((ssparts.data_ptr(), ssparts.numel(), 1.0))
             keep.append(ssparts)
+        if supw != 0:
+            lw = _sup_level_weights(cfg.suplw, ns)
+            supparts, _, supplanes = _sup_fwd(fl, cfg.gt, cfg.supq, cfg.supeps,
+                                              [supw * v for v in lw], want_grad)
+            groups.append((supparts.data_ptr(), supparts.numel(), 1.0))
+            keep.append(supparts)
         if sw != 0:
             cv, ch = _smooth_coefs(n, hs, ws_, sw, cfg.order)
             sparts = _smooth_fwd(pyr, fl, cfg.edge_alpha, cfg.eps, cv, ch, cfg.order)
@@ -2450,15 +2532,17 @@ class _Loss(torch.autograd.Function):
              _arr(C.c_int, [g[1] for g in groups]), _arr(C.c_float, [g[2] for g in groups]),
              len(groups), _ptr(loss), _stream())
         # Saved: only what a backward of a term that is on reads.  The pyramid: photometric,
-        # and smoothness with edge_alpha != 0; the flows: photometric and smoothness; census
-        # and SSIM keep just their planes.
+        # and smoothness with edge_alpha != 0; the flows: photometric and smoothness; census,
+        # SSIM and the supervised term keep just their planes.
         keep_pyr = pyr if pw != 0 or (sw != 0 and cfg.edge_alpha != 0) else []
         keep_fl = fl if pw != 0 or sw != 0 else []
-        ctx.save_for_backward(*keep_pyr, *keep_fl, *(planes or []), *(splanes or []))
+        ctx.save_for_backward(*keep_pyr, *keep_fl, *(planes or []), *(splanes or []),
+                              *(supplanes or []))
         ctx.split = (len(keep_pyr), len(keep_pyr) + len(keep_fl),
-                     len(keep_pyr) + len(keep_fl) + len(planes or []))
+                     len(keep_pyr) + len(keep_fl) + len(planes or []),
+                     len(keep_pyr) + len(keep_fl) + len(planes or []) + len(splanes or []))
         ctx.wts = cfg.wts if pw != 0 else None      # the photometric backward reads them again
-        ctx.cfg = cfg._replace(wts=None)
+        ctx.cfg = cfg._replace(wts=None, gt=None)
         ctx.coefs = (coefs, ccoefs, cv, ch, scoefs)
         return loss
 
@@ -2467,10 +2551,11 @@ class _Loss(torch.autograd.Function):
         cfg = ctx.cfg
         coefs, ccoefs, cv, ch, scoefs = ctx.coefs
         saved = ctx.saved_tensors
-        a, b, c = ctx.split
-        pyr, flows, planes, splanes = saved[:a], saved[a:b], saved[b:c], saved[c:]
+        a, b, c, d = ctx.split
+        pyr, flows, planes, splanes = saved[:a], saved[a:b], saved[b:c], saved[c:d]
+        supplanes = saved[d:]
         dloss = dloss.contiguous()
-        grads, lv = _grad_targets(cfg.fgs, flows or planes or splanes,
+        grads, lv = _grad_targets(cfg.fgs, flows or planes or splanes or supplanes,
                                   ctx.needs_input_grad[2:])
         if lv:
             written = 0                # the first term present writes, the others add
@@ -2482,6 +2567,9 @@ class _Loss(torch.autograd.Function):
                 written = 1
             if cfg.ssw != 0:
                 _ssim_bwd(splanes, lv, scoefs, dloss, written)
+                written = 1
+            if cfg.supw != 0:
+                _sup_bwd(supplanes, lv, dloss, written)
                 written = 1
             if cfg.sw != 0:
                 _smooth_bwd(pyr, flows, lv, cfg.edge_alpha, cfg.eps, cv, ch, dloss, written,
@@ -2560,7 +2648,9 @@ def _pixel_weights(weights, flows):
 
 def census_flow_loss(batch_imgs, flows, census_weight, census_radius=3, photometric_weight=1.0,
                      smoothness_weight=0.0, edge_alpha=0.0, eps=1e-4, convention="reference",
-                     weights=None, ssim_weight=0.0, smoothness_order=1):
+                     weights=None, ssim_weight=0.0, supervised_weight=0.0, supervised_q=1.0,
+                     supervised_eps=0.01, supervised_level_weights=None, gt=None,
+                     smoothness_order=1):
     """The training loss with the census data term: ``photometric_weight`` times
     photometric_loss plus ``census_weight`` times census_loss plus ``ssim_weight`` times
     ssim_loss plus ``smoothness_weight`` times flow_smoothness (of ``smoothness_order`` 1 or
@@ -2571,17 +2661,62 @@ def census_flow_loss(batch_imgs, flows, census_weight, census_radius=3, photomet
     terms (occlusion_masks' output, or None for a level of weight 1).  They are constants; a
     pixel's photometric error, its census window sum and the SSIM error of the window centred
     on it are multiplied by its weight, the normalisers stay the means over all pixels (all
-    windows), and the smoothness term is not weighted."""
+    windows), and the smoothness term is not weighted.
+
+    ``supervised_weight`` > 0 adds that weight times supervised_flow_loss against ``gt`` (image
+    convention only); the three data weights may then all be 0.  ``gt`` may hold fewer images
+    than the flows: it belongs to the first ones (the forward pairs of a forward-backward
+    batch).  The pixel weights do not weigh the supervised term."""
     wts = _pixel_weights(weights, flows) if weights is not None else None
+    sup = {}
+    if supervised_weight != 0:
+        sup = _sup_cfg(flows, gt, supervised_weight, supervised_q, supervised_eps,
+                       supervised_level_weights, convention)
+    elif gt is not None:
+        raise ValueError("ground truth given, but supervised_weight is 0")
     cfg = _LossCfg(pw=float(photometric_weight), cw=float(census_weight),
                    radius=_census_radius(census_radius), sw=float(smoothness_weight),
                    edge_alpha=float(edge_alpha), eps=float(eps),
                    order=_smooth_order(smoothness_order),
                    wc=warp_convention(convention), wts=wts, fgs=_flowgrads(flows),
-                   ssw=float(ssim_weight))
-    assert cfg.pw != 0 or cfg.cw != 0 or cfg.ssw != 0, \
+                   ssw=float(ssim_weight), **sup)
+    assert cfg.pw != 0 or cfg.cw != 0 or cfg.ssw != 0 or cfg.supw != 0, \
         "a data term is needed: all three data weights are 0"
     return _Loss.apply(batch_imgs, cfg, *flows)
+
+
+def _sup_cfg(flows, gt, weight, q, eps, level_weights, convention="image"):
+    """The supervised fields of a _LossCfg, checked."""
+    if warp_convention(convention) != _lib.WARP_IMAGE:
+        raise ValueError("the supervised term needs the image warp convention: a %r-convention "
+                         "flow is not a displacement" % (convention,))
+    if not weight > 0:
+        raise ValueError("supervised weight must be > 0, got %r" % (weight,))
+    if not 0 < q <= 2:
+        raise ValueError("supervised q must be in (0, 2], got %r" % (q,))
+    if not eps > 0:
+        raise ValueError("supervised eps must be > 0, got %r" % (eps,))
+    if gt is None:
+        raise ValueError("the supervised term needs ground truth (gt)")
+    if not 1 <= len(flows) <= 8:
+        raise ValueError("the supervised term takes 1..8 levels, got %d" % len(flows))
+    lw = _sup_level_weights(level_weights, len(flows))
+    _check_dev(*flows)
+    return dict(supw=float(weight), supq=float(q), supeps=float(eps), suplw=lw,
+                gt=_gt_handle(gt, flows[0].shape[0]))
+
+
+def supervised_flow_loss(flows, gt, q=1.0, eps=0.01, level_weights=None):
+    """The supervised term alone (a scalar; plain gradients for the flows): the sum over the
+    levels of ``level_weights`` (default 1 / levels each) times the mean over the images with
+    a valid pixel of the mean over an image's valid pixels of (|u - gt|^2 + eps^2)^(q/2), u the
+    level's flow upsampled to the map's native size as evaluate.flow_metrics samples it, in
+    native pixels (DESIGN.md "Supervised term").  ``gt``: the n images' KITTI flow maps as a
+    list of (h, w, 3) uint16 arrays, pack_gt_raw's buffer (numpy or CUDA), or the pair
+    (buffer, descriptors).  No image pyramid is built."""
+    flows = list(flows)
+    cfg = _LossCfg(**_sup_cfg(flows, gt, 1.0, q, eps, level_weights))
+    return _Loss.apply(None, cfg, *flows)
 
 
 # ============================================================== occlusion masks =====

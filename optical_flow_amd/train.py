@@ -10,12 +10,18 @@ PNGs.  No TensorBoard writer (a JSONL step log instead).  Data parallelism (one 
 GPU, RCCL all-reduce of gradient buckets overlapped with the backward) is build-added; with
 KITTI each rank reads its own seeded shuffle.  ``--augment`` (KITTI only) switches on the
 seeded GPU augmentation of data_reader.AugmentOpts: random zoom / crop, flip, colour jitter.
+``--kitti-flow ROOT`` reads the labelled frames of a KITTI 2015 flow tree instead and, with
+``--supervised-weight`` > 0, fine-tunes on their sparse ground truth (evaluate.KittiFlowReader;
+``--kitti-flow-holdout K`` keeps every K-th frame for evaluation).
 ``--clip-norm C`` / ``--skip-nonfinite`` / ``--log-grad-norm`` switch on KerasAdam's global-norm
 clipping, its non-finite update guard and the per-step gradient norm in the step log.
 
 Run:  python -m optical_flow_amd.train --height 384 --width 512 --batch 8 --steps 20
       python -m optical_flow_amd.train --kitti /data/kitti_raw --epochs 20
       python -m optical_flow_amd.train --kitti /data/kitti_raw --epochs 20 --augment
+      python -m optical_flow_amd.train --kitti-flow /data/kitti_flow --warp-convention image \\
+          --photometric-weight 0 --supervised-weight 1 --supervised-q 0.4 \\
+          --kitti-flow-holdout 5 --pretrained ckpt/flow_net_19/weights
 """
 from __future__ import annotations
 
@@ -211,7 +217,9 @@ class Trainer:
                 comm = make_comm(kind, rank, world)
             self.reducer = GradBucketReducer(flow_net.store, comm=comm)
 
-    def train_step(self, batch_imgs, step_count=0):
+    def train_step(self, batch_imgs, step_count=0, gt=None):
+        """``gt``: the batch's KITTI flow ground truth for a loss layer with
+        ``supervised_weight`` > 0 (what LossLayer's call takes); None otherwise."""
         store = self.flow_net.store
         store.zero_grad()
         if self.reducer is not None:
@@ -224,7 +232,10 @@ class Trainer:
             batch_imgs = torch.cat([batch_imgs,
                                     torch.cat([batch_imgs[..., 3:], batch_imgs[..., :3]], -1)], 0)
         flows = self.flow_net(batch_imgs)
-        loss_value = self.loss_layer(batch_imgs, flows)
+        if gt is not None:
+            loss_value = self.loss_layer(batch_imgs, flows, gt=gt)
+        else:                           # as it always was (a custom loss takes two arguments)
+            loss_value = self.loss_layer(batch_imgs, flows)
         loss_value.backward()
         scale = 1.0
         if self.reducer is not None:
@@ -276,6 +287,10 @@ class GraphedStep:
         if trainer.reducer is not None and getattr(trainer.reducer.comm, "kind", "") != "rccl":
             raise RuntimeError("graph capture needs the RCCL communicator (gloo collectives "
                                "cannot be captured)")
+        if getattr(trainer.loss_layer, "supervised_weight", 0.0) != 0.0:
+            raise RuntimeError("graph capture does not take a supervised loss layer "
+                               "(supervised_weight > 0): the ground-truth buffer changes size "
+                               "from batch to batch; run train_step(batch, gt=...) eagerly")
         self.trainer = trainer
         self.batch = batch_imgs
         cur = torch.cuda.current_stream()
@@ -423,6 +438,20 @@ def build_parser():
     ap.add_argument("--occ-alpha2", type=float, default=0.5,
                     help="absolute tolerance of the forward-backward check, in squared "
                          "full-resolution pixels")
+    ap.add_argument("--kitti-flow", default=None, metavar="ROOT",
+                    help="train on the labelled frames of a KITTI 2015 flow tree (supervised "
+                         "fine-tuning; excludes --kitti, no augmentation)")
+    ap.add_argument("--kitti-flow-holdout", type=int, default=0, metavar="K",
+                    help="with --kitti-flow: keep every K-th frame out of training and evaluate "
+                         "on those after every --eval-every epochs and at the end")
+    ap.add_argument("--supervised-weight", type=float, default=0.0,
+                    help="weight of the supervised end-point-error term against the ground "
+                         "truth (0: off); needs --kitti-flow and --warp-convention image")
+    ap.add_argument("--supervised-q", type=float, default=1.0,
+                    help="exponent of the supervised penalty (|e|^2 + eps^2)^(q/2); 0.4 is the "
+                         "robust fine-tuning penalty of the PWC-Net family")
+    ap.add_argument("--supervised-eps", type=float, default=0.01,
+                    help="eps of the supervised penalty, in native pixels")
     ap.add_argument("--eval-kitti-flow", default=None, metavar="ROOT",
                     help="KITTI 2015 flow root: EPE and Fl-all against its ground truth after "
                          "every --eval-every epochs and at the end (needs --warp-convention image)")
@@ -465,6 +494,33 @@ def check_eval_args(args):
         raise ValueError("--eval-every must be >= 1, got %d" % args.eval_every)
 
 
+def check_supervised_args(args):
+    """--kitti-flow excludes --kitti; --supervised-weight > 0 needs --kitti-flow (the labelled
+    frames) and --warp-convention image; --kitti-flow-holdout needs --kitti-flow and is 0 (off)
+    or >= 2.  ValueError otherwise (main turns it into a parser error)."""
+    if args.kitti_flow is not None and args.kitti is not None:
+        raise ValueError("--kitti-flow and --kitti exclude each other: one run reads one data set")
+    if args.supervised_weight < 0:
+        raise ValueError("--supervised-weight must be >= 0, got %r" % (args.supervised_weight,))
+    if args.supervised_weight > 0:
+        if args.kitti_flow is None:
+            raise ValueError("--supervised-weight > 0 needs --kitti-flow: only its frames carry "
+                             "ground truth")
+        if args.warp_convention != "image":
+            raise ValueError("--supervised-weight > 0 needs --warp-convention image: a "
+                             "reference-convention flow is not an image displacement")
+    if args.kitti_flow_holdout:
+        if args.kitti_flow is None:
+            raise ValueError("--kitti-flow-holdout needs --kitti-flow")
+        if args.kitti_flow_holdout < 2:
+            raise ValueError("--kitti-flow-holdout must be >= 2, got %d" % args.kitti_flow_holdout)
+        if args.warp_convention != "image":
+            raise ValueError("--kitti-flow-holdout evaluates image displacements: it needs "
+                             "--warp-convention image")
+        if args.eval_every < 1:
+            raise ValueError("--eval-every must be >= 1, got %d" % args.eval_every)
+
+
 def check_occlusion_args(args):
     """--occlusion masks are defined on image displacements, so anything but "none" needs
     --warp-convention image; the alphas are >= 0.  ValueError otherwise (main turns it into a
@@ -489,8 +545,9 @@ def header_record(args, augment=None):
     occ = (args.occlusion != "none" or args.occ_alpha1 != 0.01 or args.occ_alpha2 != 0.5)
     order2 = getattr(args, "smoothness_order", 1) == 2
     ssim = getattr(args, "ssim_weight", 0.0)
+    sup = getattr(args, "supervised_weight", 0.0)
     if not (args.smoothness_weight or args.edge_alpha or augment is not None or census or clip
-            or image or occ or order2 or ssim):
+            or image or occ or order2 or ssim or sup):
         return None
     head = {"header": True, "smoothness_weight": args.smoothness_weight,
             "edge_alpha": args.edge_alpha}
@@ -498,6 +555,10 @@ def header_record(args, augment=None):
         head["smoothness_order"] = 2
     if ssim:                        # logs without the SSIM term stay what they were
         head["ssim_weight"] = ssim
+    if sup:                         # logs without the supervised term stay what they were
+        head.update(supervised_weight=sup, supervised_q=args.supervised_q,
+                    supervised_eps=args.supervised_eps, kitti_flow=args.kitti_flow,
+                    kitti_flow_holdout=args.kitti_flow_holdout)
     if census:
         head.update(census_weight=args.census_weight, census_radius=args.census_radius,
                     photometric_weight=args.photometric_weight)
@@ -523,6 +584,9 @@ def main(argv=None):
         augment = augment_from_args(args)
     except ValueError as e:
         ap.error(str(e))
+    if augment is not None and args.kitti_flow:
+        ap.error("--augment / --aug-* do not apply with --kitti-flow: a spatial augmentation "
+                 "would have to move the ground truth with the frame")
     if augment is not None and not args.kitti:
         ap.error("--augment / --aug-* apply only with --kitti: without it the driver trains on "
                  "synthetic pairs, which are not augmented")
@@ -530,6 +594,7 @@ def main(argv=None):
     try:
         check_eval_args(args)
         check_occlusion_args(args)
+        check_supervised_args(args)
     except ValueError as e:
         ap.error(str(e))
 
@@ -542,7 +607,10 @@ def main(argv=None):
                                occlusion=args.occlusion, occlusion_alpha1=args.occ_alpha1,
                                occlusion_alpha2=args.occ_alpha2,
                                smoothness_order=args.smoothness_order,
-                               ssim_weight=args.ssim_weight)
+                               ssim_weight=args.ssim_weight,
+                               supervised_weight=args.supervised_weight,
+                               supervised_q=args.supervised_q,
+                               supervised_eps=args.supervised_eps)
     except ValueError as e:
         ap.error(str(e))
     try:
@@ -569,8 +637,19 @@ def main(argv=None):
         from .data_reader import AsyncReader, ReaderOpts
         reader = AsyncReader(ReaderOpts(args.kitti, args.batch, args.height, args.width,
                                         args.nworkers, seed=args.seed + rank, augment=augment))
-    nbatches = reader.nbatches if reader is not None else args.steps
+    labelled = None
     eval_frames = None
+    if args.kitti_flow:
+        from .evaluate import KittiFlowReader, evaluate, list_kitti_flow, split_kitti_flow
+        frames = list_kitti_flow(args.kitti_flow)
+        if args.kitti_flow_holdout:
+            frames, held = split_kitti_flow(frames, args.kitti_flow_holdout)
+            if rank == 0:
+                eval_frames = held
+        labelled = KittiFlowReader(frames, args.batch, args.height, args.width,
+                                   nworkers=args.nworkers, seed=args.seed + rank)
+    nbatches = (reader.nbatches if reader is not None else
+                labelled.nbatches if labelled is not None else args.steps)
     if args.eval_kitti_flow is not None and rank == 0:
         from .evaluate import evaluate, list_kitti_flow
         eval_frames = list_kitti_flow(args.eval_kitti_flow)      # a bad root fails before training
@@ -579,13 +658,19 @@ def main(argv=None):
         if epoch == args.lr_drop_epoch:
             opt.learning_rate = args.lr * 0.1
         t0 = time.time()
+        epoch_batches = iter(labelled) if labelled is not None else None
         for b in range(nbatches):
-            if reader is not None:
+            gt = None
+            if epoch_batches is not None:
+                batch, gt_raw, descs = next(epoch_batches)
+                if args.supervised_weight > 0:
+                    gt = (gt_raw, descs)
+            elif reader is not None:
                 batch = reader.get_batch()
             else:
                 batch = torch.from_numpy(synthetic_batch(args.batch, args.height, args.width,
                                                          seed=1234 + step, rank=rank)).cuda()
-            loss, flows = trainer.train_step(batch, step)
+            loss, flows = trainer.train_step(batch, step, gt=gt)
             lv = float(loss)
             if rank == 0:
                 sys.stdout.write("\rbatch %d/%d, loss: %.2e    " % (b + 1, nbatches, lv))
