@@ -973,6 +973,72 @@ int of_supervised_fwd_multi(const float* const* flows, int n, int n_gt, const in
                             int64_t workspace_bytes, float* const* dsdfs, float* partials,
                             void* stream);
 
+/* ==== Augmentation self-supervision (build-added; the reference has none): the net's own flow
+ * on the un-augmented batch (the teacher), carried through an of_augment record, is the target
+ * of the flow it predicts on the augmented batch (the student).  Image convention only
+ * (OF_WARP_IMAGE: a flow is an image displacement, channel 0 along x).  No atomics, no
+ * allocation, no host read or sync; every output element is written; run-to-run bitwise equal. */
+
+/* of_augment_pairs' map, tap and colour stage on a batch that is already preprocessed floats:
+ * batch (n, h, w, 6) fp32 (channels 0..2 image 1, 3..5 image 2, means subtracted) + n records in
+ * device memory (record b serves both images of pair b) -> out (n, h, w, 6).  Per output pixel
+ * (x, y), all in float32 in this order, no contraction (tests/selfsup_ref.py restates it bit for
+ * bit):
+ *   u, v from m as in of_augment_pairs;  sx = u*(float)w - 0.5f, sy = v*(float)h - 0.5f, clamped
+ *   to [0, w-1] / [0, h-1];  x0 = floor(sx), x1 = min(x0+1, w-1), fx = sx - x0 (same for y);
+ *   per channel c < 6 on the float taps: top = p00 + (p01-p00)*fx, bot = p10 + (p11-p10)*fx,
+ *   x = top + (bot-top)*fy;
+ *   if flags & 1, per image: val = (float)((double)x + mean[c]), then of_augment_pairs' colour
+ *   stage on the image's three values (gain, brightness, contrast, saturation, clamp to [0, 1]),
+ *   then out = (float)((double)val - mean[c]);  else out = x.
+ * The taps stay inside the frame for any record, finite or not.  OF_EINVAL (and no launch) for a
+ * NULL pointer, batch == out, batch or out not 8-byte aligned, n < 0 or > 65535, h or w < 1 or
+ * h*w >= 2^31 - 256.  n == 0 launches nothing. */
+int of_augment_batch(const float* batch, int n, int h, int w, const of_augment* dev_params,
+                     float* out, void* stream);
+
+/* A teacher flow moved through the records: teacher (n, fh, fw, 2) fp32 in cells of its own grid,
+ * records drawn for an img_h x img_w image, teacher_mask (n, fh, fw) or NULL (= ones) ->
+ * target (n, fh, fw, 2), weight (n, fh, fw).  For student cell (i, j) of image b, in fp32:
+ *   xc = (j + 0.5) * img_w / fw,  yc = (i + 0.5) * img_h / fh;
+ *   u = (m0*xc + m1*yc) + m2,  v = (m3*xc + m4*yc) + m5;
+ *   px = u*fw - 0.5,  py = v*fh - 0.5       (where the student cell lies on the teacher grid);
+ *   t = the teacher sampled bilinearly at (px, py): px, py clamped to [0, fw-1] / [0, fh-1],
+ *       x0 = floor, x1 = min(x0+1, fw-1), fx = px - x0 (same for y), top / bot form as above;
+ *   inside  = 0 <= px <= fw-1 and 0 <= py <= fh-1;
+ *   visible = the same bounds on (px + t.x, py + t.y)   (of_occ_mask_multi's border criterion,
+ *             applied to the teacher);
+ *   A = [[m0*img_w, m1*img_h*fw/fh], [m3*img_w*fh/fw, m4*img_h]]   (the map's linear part in cells);
+ *   target = A^-1 t   (a horizontal flip negates t.x, a zoom z gives z*t);
+ *   weight = inside && visible ? teacher_mask sampled at (px, py) with the same taps : 0.
+ * If |det A| < 1e-12 (or is not a number), the target and the weight of every cell of that image
+ * are 0.  OF_EINVAL (and no launch) for a NULL teacher / dev_params / target / weight, teacher ==
+ * target, teacher or target not 8-byte aligned, n < 0 or > 65535, a size < 1, fh*fw >= 2^31 - 256.
+ * n == 0 launches nothing. */
+int of_flow_transform(const float* teacher, int n, int fh, int fw, int img_h, int img_w,
+                      const of_augment* dev_params, const float* teacher_mask, float* target,
+                      float* weight, void* stream);
+
+/* Dense flow-to-flow penalty of the student against the target: with e = s - t per cell,
+ *   S = sum over the n*fh*fw cells of weight * (e_x^2 + e_y^2 + eps^2)^(q/2)
+ * (fp32; q == 1: sqrtf, else exp2(q/2 * log2(.)), the supervised term's form; a cell of weight
+ * exactly 0 contributes exactly 0 whatever its flows hold).  `partials`
+ * (of_flow_distill_partials(n, fh, fw) floats, one per workgroup of 1024 consecutive cells: a
+ * thread sums its four cells in double, then a wave shuffle tree, then the workgroup's waves in
+ * wave order through LDS) sums to coef * S and of_sum_partials reduces it.  plane (n, fh, fw, 2),
+ * when not NULL, receives d(coef * S) / d student = coef * weight * q * (|e|^2 + eps^2)^(q/2 - 1)
+ * * e, every element written; NULL: the value only.  of_census_bwd_multi (coefs 1) scales the
+ * plane by dloss into d(flow).  The target and the weight are constants.  Flows and plane that
+ * are 16-byte and a weight that is 8-byte aligned are read and written two cells at a time.
+ * of_flow_distill_partials is 0 for a size < 1 or n*fh*fw >= 2^31 - 1024.  OF_EINVAL (and no
+ * launch) for a NULL student / target / weight / partials, n or a grid size < 1, n*fh*fw >=
+ * 2^31 - 1024, q outside (0, 2], eps <= 0 or not finite, student / target / plane not 8-byte or
+ * weight / partials not 4-byte aligned. */
+int of_flow_distill_partials(int n, int fh, int fw);
+int of_flow_distill_fwd(const float* student, const float* target, const float* weight, int n,
+                        int fh, int fw, float q, float eps, float coef, float* plane,
+                        float* partials, void* stream);
+
 /* ==== SURVEY.md §8 f row 2: TensorFlow checkpoint bundles (save_weights / load_weights) ===== */
 
 /* CRC32C (Castagnoli) of n bytes, continuing from crc (0 to start; unmasked).  The bundle's

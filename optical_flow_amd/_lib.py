@@ -231,6 +231,12 @@ PROTOTYPES = {
     "of_supervised_workspace_bytes": (I64, [I, I, I]),
     "of_supervised_fwd_multi": (I, [C.POINTER(P), I, I, C.POINTER(I), C.POINTER(I), I, P, P, I64,
                                     I, I, F, F, C.POINTER(F), P, I64, C.POINTER(P), P, P]),
+    # augmentation self-supervision: the records are of_augment_pairs'; the distill term's
+    # backward is the census one
+    "of_augment_batch": (I, [P, I, I, I, P, P, P]),
+    "of_flow_transform": (I, [P, I, I, I, I, I, P, P, P, P, P]),
+    "of_flow_distill_partials": (I, [I, I, I]),
+    "of_flow_distill_fwd": (I, [P, P, P, I, I, I, F, F, F, P, P, P]),
     "of_stem_bwd_fused_workspace": (SZ, [PD, I]),
     "of_stem_bwd_fused": (I, [PD, I, P, I, P, P, P, P, P, P, F, P, P, P, P, I, P, SZ, P]),
     # BatchNormalization in training mode (bn_mode="training")

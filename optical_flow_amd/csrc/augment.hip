@@ -10,6 +10,7 @@
 // The arithmetic is defined step by step in include/oflow.h (of_augment_pairs) and restated in
 // numpy float32 by tests/augment_np.py, which the kernel matches bit for bit: IEEE single ops
 // in exactly that order, floating-point contraction off, correctly rounded divisions.
+#include "augment_colour.h"
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -43,24 +44,7 @@ __device__ __forceinline__ void augment_pixel(const uint8_t* __restrict__ raw,
     const float bot = p10 + (p11 - p10) * fx;
     val[c] = __fdiv_rn(top + (bot - top) * fy, 255.0f);
   }
-  if (a.flags & 1) {
-    for (int c = 0; c < 3; ++c) {
-      val[c] *= a.gain[c];
-      val[c] += a.brightness;
-      val[c] = (val[c] - 0.5f) * a.contrast + 0.5f;
-    }
-    const float gray = (0.114f * val[0] + 0.587f * val[1]) + 0.299f * val[2];
-    for (int c = 0; c < 3; ++c) {
-      val[c] = gray + (val[c] - gray) * a.saturation;
-      val[c] = fminf(fmaxf(val[c], 0.f), 1.f);
-    }
-  }
-}
-
-// image_ops.hip's normalise() on a float value: minus the float64 mean, rounded to float.
-__device__ __forceinline__ float sub_mean(float v, int c) {
-  const double mean = c == 0 ? 123.0 / 255.0 : c == 1 ? 117.0 / 255.0 : 104.0 / 255.0;
-  return (float)((double)v - mean);
+  if (a.flags & 1) augment_colour(a, val);     // augment_colour.h, shared with selfsup.hip
 }
 
 // grid = (cdiv(oh * ow, 256), npairs): the pair's record and its two image descriptors are

@@ -57,14 +57,21 @@ class LossLayer:
     (ops.supervised_flow_loss; DESIGN.md "Supervised term").  With it the three unsupervised
     data weights may all be 0 (pure fine-tuning).  With ``occlusion="fb"`` it scores the
     forward pairs only (the first half of the doubled batch); the occlusion masks do not weigh
-    it."""
+    it.
+
+    ``selfsup_weight`` > 0 (build-added, image convention only) adds that weight times the
+    self-supervision term: the finest flow against a target that ops.transform_flow carried over
+    from a teacher pass on the un-augmented batch, passed to the call as ``selfsup`` = (target,
+    weight); the penalty weight * (|flow - target|^2 + selfsup_eps^2)^(selfsup_q / 2) is averaged
+    over all cells of the target's images (ops.selfsup_flow_loss; DESIGN.md "Self-supervision";
+    Trainer(selfsup=...) runs the teacher pass).  It is no data term: the loss still needs one."""
 
     def __init__(self, smoothness_weight=0.0, edge_alpha=0.0, smoothness_eps=1e-4,
                  census_weight=0.0, census_radius=3, photometric_weight=1.0,
                  warp_convention="reference", occlusion="none", occlusion_alpha1=0.01,
                  occlusion_alpha2=0.5, ssim_weight=0.0, supervised_weight=0.0,
                  supervised_q=1.0, supervised_eps=0.01, supervised_level_weights=None,
-                 smoothness_order=1):
+                 selfsup_weight=0.0, selfsup_q=0.4, selfsup_eps=0.01, smoothness_order=1):
         ops.warp_convention(warp_convention)
         self.warp_convention = warp_convention
         if occlusion not in ("none", "border", "fb"):
@@ -108,6 +115,19 @@ class LossLayer:
             raise ValueError("supervised_weight > 0 needs warp_convention='image': a "
                              "%r-convention flow is not a displacement, its error against "
                              "ground truth means nothing" % (warp_convention,))
+        if not selfsup_weight >= 0:
+            raise ValueError("selfsup_weight must be >= 0, got %r" % (selfsup_weight,))
+        if not 0 < selfsup_q <= 2:
+            raise ValueError("selfsup_q must be in (0, 2], got %r" % (selfsup_q,))
+        if not selfsup_eps > 0:
+            raise ValueError("selfsup_eps must be > 0, got %r" % (selfsup_eps,))
+        if selfsup_weight > 0 and warp_convention != "image":
+            raise ValueError("selfsup_weight > 0 needs warp_convention='image': a %r-convention "
+                             "flow is not a displacement, an augmentation cannot carry it"
+                             % (warp_convention,))
+        self.selfsup_weight = float(selfsup_weight)
+        self.selfsup_q = float(selfsup_q)
+        self.selfsup_eps = float(selfsup_eps)
         self.supervised_weight = float(supervised_weight)
         self.supervised_q = float(supervised_q)
         self.supervised_eps = float(supervised_eps)
@@ -127,7 +147,12 @@ class LossLayer:
         self.photometric_weight = float(photometric_weight)
         self.ssim_weight = float(ssim_weight)
 
-    def __call__(self, batch_imgs, flows, gt=None):
+    def __call__(self, batch_imgs, flows, gt=None, selfsup=None):
+        if self.selfsup_weight > 0 and selfsup is None:
+            raise ValueError("selfsup_weight > 0: the call needs the (target, weight) pair "
+                             "(selfsup)")
+        if self.selfsup_weight == 0 and selfsup is not None:
+            raise ValueError("self-supervision target given, but selfsup_weight is 0")
         if self.supervised_weight > 0 and gt is None:
             raise ValueError("supervised_weight > 0: the call needs the ground truth (gt)")
         if self.supervised_weight == 0 and gt is not None:
@@ -144,6 +169,9 @@ class LossLayer:
         order = {"smoothness_order": 2} if self.smoothness_order == 2 else {}
         if self.ssim_weight != 0.0:     # without it the ops entries are called as before
             order["ssim_weight"] = self.ssim_weight
+        if self.selfsup_weight != 0.0:
+            order.update(selfsup_weight=self.selfsup_weight, selfsup_q=self.selfsup_q,
+                         selfsup_eps=self.selfsup_eps, selfsup=selfsup)
         if self.supervised_weight != 0.0:
             if self.supervised_level_weights is not None and \
                     len(self.supervised_level_weights) != num_scales:
@@ -172,7 +200,7 @@ class LossLayer:
                                         self.smoothness_eps, self.warp_convention, weights=masks,
                                         **order)
         if self.census_weight == 0.0 and self.photometric_weight == 1.0 and \
-                self.ssim_weight == 0.0:
+                self.ssim_weight == 0.0 and self.selfsup_weight == 0.0:
             if self.smoothness_weight == 0.0:
                 return ops.photometric_loss(batch_imgs, list(flows), self.warp_convention)
             return ops.flow_loss(batch_imgs, list(flows), self.smoothness_weight,

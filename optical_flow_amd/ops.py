@@ -2405,6 +2405,79 @@ def _sup_bwd(planes, lv, dloss, accumulate):
     _census_bwd(planes, lv, [1.0] * len(planes), dloss, accumulate)
 
 
+# ============================================================= self-supervision =====
+def _records_dev(records, n, device):
+    """``n`` of_augment records as a CUDA uint8 tensor of n * 64 bytes: an AUGMENT_DTYPE numpy
+    array is copied to ``device``, a CUDA uint8 tensor is used as it is."""
+    import numpy as np
+    from .data_reader import AUGMENT_DTYPE
+    if isinstance(records, torch.Tensor):
+        if not records.is_cuda or records.dtype != torch.uint8:
+            raise TypeError("records: expected a CUDA uint8 tensor or an AUGMENT_DTYPE array, got "
+                            "a %s %s tensor" % (records.device, records.dtype))
+        dev = records.contiguous().view(-1)
+    else:
+        host = np.ascontiguousarray(records, dtype=AUGMENT_DTYPE).reshape(-1)
+        dev = torch.from_numpy(host.view(np.uint8).copy()).to(device)
+    if dev.numel() != n * AUGMENT_DTYPE.itemsize:
+        raise ValueError("records: %d bytes for %d images (%d bytes each)"
+                         % (dev.numel(), n, AUGMENT_DTYPE.itemsize))
+    return dev
+
+
+def augment_batch(batch, records):
+    """of_augment_batch (include/oflow.h): a preprocessed (n, h, w, 6) batch moved through one
+    of_augment record per pair -- data_reader.sample_augment's, as an AUGMENT_DTYPE array or a
+    CUDA uint8 tensor -- the map, the bilinear tap and the colour stage of the reader's
+    augmentation, on floats.  No autograd: the batch is data."""
+    _check_dev(batch)
+    n, h, w, c = batch.shape
+    assert c == 6, "augment_batch takes (n, h, w, 6) pairs"
+    b = batch.detach().contiguous()
+    rec = _records_dev(records, n, b.device)
+    out = torch.empty_like(b)
+    call("of_augment_batch", _ptr(b), n, h, w, _ptr(rec), _ptr(out), _stream())
+    return out
+
+
+def transform_flow(flow, records, img_hw, mask=None):
+    """of_flow_transform (include/oflow.h): a teacher ``flow`` (n, fh, fw, 2), image convention,
+    in cells of its own grid, carried through the records (drawn for an image of ``img_hw`` =
+    (H, W)) -> (target (n, fh, fw, 2), weight (n, fh, fw)).  The target is what the flow of the
+    augmented pair should be at each of its cells; the weight is ``mask`` (default ones)
+    sampled there, 0 where the cell's source lies outside the teacher's frame or the teacher's
+    flow leaves it.  No autograd: both are constants (DESIGN.md "Self-supervision")."""
+    _check_dev(flow, mask)
+    n, fh, fw, c = flow.shape
+    assert c == 2, "transform_flow takes (n, fh, fw, 2) flows"
+    if mask is not None and tuple(mask.shape) != (n, fh, fw):
+        raise ValueError("mask has shape %s, expected %s" % (tuple(mask.shape), (n, fh, fw)))
+    f = flow.detach().contiguous()
+    mk = mask.detach().contiguous() if mask is not None else None
+    rec = _records_dev(records, n, f.device)
+    target = torch.empty_like(f)
+    weight = torch.empty((n, fh, fw), device=f.device)
+    call("of_flow_transform", _ptr(f), n, fh, fw, int(img_hw[0]), int(img_hw[1]), _ptr(rec),
+         _ptr(mk), _ptr(target), _ptr(weight), _stream())
+    return target, weight
+
+
+def _self_fwd(f0, target, weight, q, eps, coef, want_grad):
+    """of_flow_distill_fwd on the finest flow (the self-supervision term, include/oflow.h):
+    (partials, plane).  The first target.shape[0] images are scored; the partials sum to coef *
+    S; the plane, shaped like ``f0``, is d(coef * S) / d f0, every element written (zeros for the
+    images past the target's), or None without want_grad."""
+    n_t, fh, fw = target.shape[:3]
+    parts = torch.empty(_lib.lib().of_flow_distill_partials(n_t, fh, fw), device=f0.device)
+    plane = torch.empty_like(f0) if want_grad else None
+    if plane is not None and f0.shape[0] > n_t:
+        rest = plane[n_t:]
+        call("of_fill", _ptr(rest), 0.0, rest.numel(), _stream())
+    call("of_flow_distill_fwd", _ptr(f0), _ptr(target), _ptr(weight), n_t, fh, fw, q, eps, coef,
+         _ptr(plane), _ptr(parts), _stream())
+    return parts, plane
+
+
 # ============================================================ the loss Function =====
 def _flowgrads(flows):
     """Each flow's FlowGrad (None where a flow has none); if any of them does not have its
@@ -2457,12 +2530,19 @@ class _LossCfg(NamedTuple):
     supeps: float = 0.01            # ground truth as _gt_handle gives it
     suplw: Optional[tuple] = None
     gt: Optional[tuple] = None
+    selfw: float = 0.0              # self-supervision term: its weight, the penalty's exponent
+    selfq: float = 0.4              # and eps, and the (target, weight) pair of
+    selfeps: float = 0.01           # transform_flow for the first target.shape[0] images of
+    selftw: Optional[tuple] = None  # the finest flow
 
 
 class _Loss(torch.autograd.Function):
-    """pw * photometric + cw * census + ssw * SSIM + supw * supervised + sw * smoothness, each
+    """pw * photometric + cw * census + ssw * SSIM + supw * supervised + selfw * self-supervision
+    + sw * smoothness, each
     the mean over the levels of that level's mean (the supervised term: its own level weights,
-    against the ground truth ``cfg.gt``), on one image pyramid; the images are constants.  A term whose
+    against the ground truth ``cfg.gt``; the self-supervision term: the finest flow only, against
+    ``cfg.selftw``, the mean over all cells of its first images), on one image pyramid; the images
+    are constants.  A term whose
     weight is 0 launches nothing, and the pyramid is only built when a term reads it (a data
     term, or the smoothness term with edge_alpha != 0).  The smoothness term is never weighted
     by ``wts``.
@@ -2470,7 +2550,8 @@ class _Loss(torch.autograd.Function):
     One Function for all terms because of the FlowGrad protocol: the loss writes a flow's
     gradient buffer once and upscale_flow's backward adds to it afterwards, so two Functions
     returning gradients for the same flow would break it.  In the backward the terms run
-    photometric, census, SSIM, supervised, smoothness; the first one present overwrites each level's
+    photometric, census, SSIM, supervised, self-supervision (level 0 only), smoothness; the first
+    one present overwrites each level's
     d(flow) output and the later ones add into it (``accumulate = 1``)."""
 
     @staticmethod
@@ -2479,10 +2560,16 @@ class _Loss(torch.autograd.Function):
         _check_dev(batch_imgs, *flows)
         ns = len(flows)
         assert 1 <= ns <= 8, "the loss kernels take 8 levels"
-        supw = cfg.supw
-        assert (ns if pw else 0) + (cw != 0) + (ssw != 0) + (sw != 0) + (supw != 0) <= 8, \
-            "of_sum_partials takes 8 groups: one per photometric level, census, SSIM, " \
-            "supervised, smoothness"
+        supw, selfw = cfg.supw, cfg.selfw
+        ngroups = ((ns if pw else 0) + (cw != 0) + (ssw != 0) + (sw != 0) + (supw != 0) +
+                   (selfw != 0))
+        if ngroups > 8:
+            raise ValueError("of_sum_partials takes 8 groups (one per photometric level, census, "
+                             "SSIM, supervised, self-supervision, smoothness): this loss needs %d"
+                             % ngroups)
+        # the self-supervision term writes level 0 alone: it may open the backward only when
+        # there is no other level
+        assert selfw == 0 or ns == 1 or pw != 0 or cw != 0 or ssw != 0 or supw != 0
         fl = [f.contiguous() for f in flows]
         n = fl[0].shape[0]
         hs = [f.shape[1] for f in fl]
@@ -2496,7 +2583,7 @@ class _Loss(torch.autograd.Function):
         # term's partials or to ``loss`` and be overwritten ahead of the sum on this stream.
         groups, keep = [], []
         coefs = ccoefs = scoefs = cv = ch = planes = splanes = None    # of the terms that are off
-        supplanes = None
+        supplanes = selfplane = None
         if pw != 0:
             coefs = [pw / (ns * n * h * w * 3) for h, w in zip(hs, ws_)]
             parts, nparts = _photo_fwd(pyr, fl, cfg.wts, cfg.wc)
@@ -2522,6 +2609,12 @@ class _Loss(torch.autograd.Function):
                                               [supw * v for v in lw], want_grad)
             groups.append((supparts.data_ptr(), supparts.numel(), 1.0))
             keep.append(supparts)
+        if selfw != 0:
+            tgt, wt = cfg.selftw
+            selfparts, selfplane = _self_fwd(fl[0], tgt, wt, cfg.selfq, cfg.selfeps,
+                                             selfw / (tgt.shape[0] * hs[0] * ws_[0]), want_grad)
+            groups.append((selfparts.data_ptr(), selfparts.numel(), 1.0))
+            keep.append(selfparts)
         if sw != 0:
             cv, ch = _smooth_coefs(n, hs, ws_, sw, cfg.order)
             sparts = _smooth_fwd(pyr, fl, cfg.edge_alpha, cfg.eps, cv, ch, cfg.order)
@@ -2533,16 +2626,18 @@ class _Loss(torch.autograd.Function):
              len(groups), _ptr(loss), _stream())
         # Saved: only what a backward of a term that is on reads.  The pyramid: photometric,
         # and smoothness with edge_alpha != 0; the flows: photometric and smoothness; census,
-        # SSIM and the supervised term keep just their planes.
+        # SSIM, the supervised and the self-supervision term keep just their planes.
         keep_pyr = pyr if pw != 0 or (sw != 0 and cfg.edge_alpha != 0) else []
         keep_fl = fl if pw != 0 or sw != 0 else []
         ctx.save_for_backward(*keep_pyr, *keep_fl, *(planes or []), *(splanes or []),
-                              *(supplanes or []))
+                              *(supplanes or []), *([selfplane] if selfplane is not None else []))
         ctx.split = (len(keep_pyr), len(keep_pyr) + len(keep_fl),
                      len(keep_pyr) + len(keep_fl) + len(planes or []),
-                     len(keep_pyr) + len(keep_fl) + len(planes or []) + len(splanes or []))
+                     len(keep_pyr) + len(keep_fl) + len(planes or []) + len(splanes or []),
+                     len(keep_pyr) + len(keep_fl) + len(planes or []) + len(splanes or []) +
+                     len(supplanes or []))
         ctx.wts = cfg.wts if pw != 0 else None      # the photometric backward reads them again
-        ctx.cfg = cfg._replace(wts=None, gt=None)
+        ctx.cfg = cfg._replace(wts=None, gt=None, selftw=None)
         ctx.coefs = (coefs, ccoefs, cv, ch, scoefs)
         return loss
 
@@ -2551,11 +2646,11 @@ class _Loss(torch.autograd.Function):
         cfg = ctx.cfg
         coefs, ccoefs, cv, ch, scoefs = ctx.coefs
         saved = ctx.saved_tensors
-        a, b, c, d = ctx.split
+        a, b, c, d, e = ctx.split
         pyr, flows, planes, splanes = saved[:a], saved[a:b], saved[b:c], saved[c:d]
-        supplanes = saved[d:]
+        supplanes, selfplanes = saved[d:e], saved[e:]
         dloss = dloss.contiguous()
-        grads, lv = _grad_targets(cfg.fgs, flows or planes or splanes or supplanes,
+        grads, lv = _grad_targets(cfg.fgs, flows or planes or splanes or supplanes or selfplanes,
                                   ctx.needs_input_grad[2:])
         if lv:
             written = 0                # the first term present writes, the others add
@@ -2570,6 +2665,10 @@ class _Loss(torch.autograd.Function):
                 written = 1
             if cfg.supw != 0:
                 _sup_bwd(supplanes, lv, dloss, written)
+                written = 1
+            lv0 = [t for t in lv if t[0] == 0]
+            if cfg.selfw != 0 and lv0:
+                _sup_bwd(selfplanes, lv0, dloss, written)
                 written = 1
             if cfg.sw != 0:
                 _smooth_bwd(pyr, flows, lv, cfg.edge_alpha, cfg.eps, cv, ch, dloss, written,
@@ -2650,6 +2749,7 @@ def census_flow_loss(batch_imgs, flows, census_weight, census_radius=3, photomet
                      smoothness_weight=0.0, edge_alpha=0.0, eps=1e-4, convention="reference",
                      weights=None, ssim_weight=0.0, supervised_weight=0.0, supervised_q=1.0,
                      supervised_eps=0.01, supervised_level_weights=None, gt=None,
+                     selfsup_weight=0.0, selfsup_q=0.4, selfsup_eps=0.01, selfsup=None,
                      smoothness_order=1):
     """The training loss with the census data term: ``photometric_weight`` times
     photometric_loss plus ``census_weight`` times census_loss plus ``ssim_weight`` times
@@ -2666,8 +2766,17 @@ def census_flow_loss(batch_imgs, flows, census_weight, census_radius=3, photomet
     ``supervised_weight`` > 0 adds that weight times supervised_flow_loss against ``gt`` (image
     convention only); the three data weights may then all be 0.  ``gt`` may hold fewer images
     than the flows: it belongs to the first ones (the forward pairs of a forward-backward
-    batch).  The pixel weights do not weigh the supervised term."""
+    batch).  The pixel weights do not weigh the supervised term.
+
+    ``selfsup_weight`` > 0 adds that weight times selfsup_flow_loss of the finest flow against
+    ``selfsup`` = transform_flow's (target, weight) (image convention only); it is no data term.
+    The pair may hold fewer images than the flows, as ``gt`` may."""
     wts = _pixel_weights(weights, flows) if weights is not None else None
+    self_ = {}
+    if selfsup_weight != 0:
+        self_ = _self_cfg(flows, selfsup, selfsup_weight, selfsup_q, selfsup_eps, convention)
+    elif selfsup is not None:
+        raise ValueError("self-supervision target given, but selfsup_weight is 0")
     sup = {}
     if supervised_weight != 0:
         sup = _sup_cfg(flows, gt, supervised_weight, supervised_q, supervised_eps,
@@ -2679,7 +2788,7 @@ def census_flow_loss(batch_imgs, flows, census_weight, census_radius=3, photomet
                    edge_alpha=float(edge_alpha), eps=float(eps),
                    order=_smooth_order(smoothness_order),
                    wc=warp_convention(convention), wts=wts, fgs=_flowgrads(flows),
-                   ssw=float(ssim_weight), **sup)
+                   ssw=float(ssim_weight), **sup, **self_)
     assert cfg.pw != 0 or cfg.cw != 0 or cfg.ssw != 0 or cfg.supw != 0, \
         "a data term is needed: all three data weights are 0"
     return _Loss.apply(batch_imgs, cfg, *flows)
@@ -2717,6 +2826,42 @@ def supervised_flow_loss(flows, gt, q=1.0, eps=0.01, level_weights=None):
     flows = list(flows)
     cfg = _LossCfg(**_sup_cfg(flows, gt, 1.0, q, eps, level_weights))
     return _Loss.apply(None, cfg, *flows)
+
+
+def _self_cfg(flows, selfsup, weight, q, eps, convention="image"):
+    """The self-supervision fields of a _LossCfg, checked."""
+    if warp_convention(convention) != _lib.WARP_IMAGE:
+        raise ValueError("the self-supervision term needs the image warp convention: a %r-"
+                         "convention flow is not a displacement" % (convention,))
+    if not weight > 0:
+        raise ValueError("selfsup weight must be > 0, got %r" % (weight,))
+    if not 0 < q <= 2:
+        raise ValueError("selfsup q must be in (0, 2], got %r" % (q,))
+    if not eps > 0:
+        raise ValueError("selfsup eps must be > 0, got %r" % (eps,))
+    if selfsup is None:
+        raise ValueError("the self-supervision term needs its (target, weight) pair (selfsup)")
+    target, wt = selfsup
+    _check_dev(flows[0], target, wt)
+    n, fh, fw = flows[0].shape[:3]
+    n_t = target.shape[0]
+    if not 1 <= n_t <= n or tuple(target.shape[1:]) != (fh, fw, 2):
+        raise ValueError("selfsup target has shape %s, expected (1..%d, %d, %d, 2): the finest "
+                         "flow's grid" % (tuple(target.shape), n, fh, fw))
+    if tuple(wt.shape) != (n_t, fh, fw):
+        raise ValueError("selfsup weight has shape %s, expected %s"
+                         % (tuple(wt.shape), (n_t, fh, fw)))
+    return dict(selfw=float(weight), selfq=float(q), selfeps=float(eps),
+                selftw=(target.detach().contiguous(), wt.detach().contiguous()))
+
+
+def selfsup_flow_loss(flow, target, weight, q=0.4, eps=0.01):
+    """The self-supervision term alone (a scalar; a plain gradient for ``flow``): the mean over
+    all cells of the first target.shape[0] images of weight * (|flow - target|^2 + eps^2)^(q/2)
+    (a cell of weight 0 counts as zero; DESIGN.md "Self-supervision").  ``target`` and ``weight``
+    are transform_flow's, constants."""
+    cfg = _LossCfg(**_self_cfg([flow], (target, weight), 1.0, q, eps))
+    return _Loss.apply(None, cfg, flow)
 
 
 # ============================================================== occlusion masks =====

@@ -13,6 +13,9 @@ seeded GPU augmentation of data_reader.AugmentOpts: random zoom / crop, flip, co
 ``--kitti-flow ROOT`` reads the labelled frames of a KITTI 2015 flow tree instead and, with
 ``--supervised-weight`` > 0, fine-tunes on their sparse ground truth (evaluate.KittiFlowReader;
 ``--kitti-flow-holdout K`` keeps every K-th frame for evaluation).
+``--selfsup-weight W`` > 0 adds augmentation self-supervision (the teacher's flow on the batch
+as read is the target on the batch moved through the ``--augment`` / ``--aug-*`` transform, on
+the device, so it also runs without ``--kitti``; ``--selfsup-start-epoch E`` starts it later).
 ``--clip-norm C`` / ``--skip-nonfinite`` / ``--log-grad-norm`` switch on KerasAdam's global-norm
 clipping, its non-finite update guard and the per-step gradient norm in the step log.
 
@@ -22,6 +25,8 @@ Run:  python -m optical_flow_amd.train --height 384 --width 512 --batch 8 --step
       python -m optical_flow_amd.train --kitti-flow /data/kitti_flow --warp-convention image \\
           --photometric-weight 0 --supervised-weight 1 --supervised-q 0.4 \\
           --kitti-flow-holdout 5 --pretrained ckpt/flow_net_19/weights
+      python -m optical_flow_amd.train --kitti /data/kitti_raw --warp-convention image \\
+          --occlusion fb --census-weight 1 --selfsup-weight 0.3 --selfsup-start-epoch 5 --augment
 """
 from __future__ import annotations
 
@@ -187,21 +192,55 @@ def check_warp_conventions(flow_net, loss_layer):
     return net_cv
 
 
+def check_selfsup(flow_net, loss_layer, selfsup):
+    """Trainer's self-supervision arguments: the AugmentOpts and a loss layer with
+    ``selfsup_weight`` > 0 need each other, and the teacher pass must not move BatchNorm's
+    moving statistics a second time.  ValueError otherwise."""
+    w = getattr(loss_layer, "selfsup_weight", 0.0)
+    if selfsup is None:
+        if w > 0:
+            raise ValueError("the loss layer has selfsup_weight > 0: the trainer needs the "
+                             "augmentation to self-supervise with (selfsup=AugmentOpts(...))")
+        return
+    from .data_reader import AugmentOpts
+    if not isinstance(selfsup, AugmentOpts):
+        raise ValueError("selfsup must be a data_reader.AugmentOpts, got %r" % (selfsup,))
+    if not w > 0:
+        raise ValueError("selfsup given, but the loss layer's selfsup_weight is 0")
+    if getattr(flow_net, "bn_mode", "inference") == "training":
+        raise ValueError("self-supervision runs a teacher pass before the step: with "
+                         "bn_mode='training' it would update the moving statistics a second "
+                         "time; use bn_mode='inference'")
+
+
 class Trainer:
     """Holds the model, optimizer, loss and (optional) DP reducer; ``train_step`` is the
     hot loop body of train.py:72-82."""
 
     def __init__(self, flow_net: FlowNet, optimizer: KerasAdam = None, loss_layer=None,
-                 data_parallel: bool = None, comm=None):
+                 data_parallel: bool = None, comm=None, selfsup=None, selfsup_seed=0):
         """data_parallel: sum the gradients over ranks before Adam (default: when a
         torch.distributed group of > 1 ranks exists).  comm: a communicator (comm.py), or
         "rccl" / "torch" to create one; default "rccl" for a GPU model (the C-ABI RCCL
-        communicator over all ranks of the default group), "torch" otherwise."""
+        communicator over all ranks of the default group), "torch" otherwise.
+
+        selfsup: a data_reader.AugmentOpts switches on augmentation self-supervision, for a
+        loss layer with ``selfsup_weight`` > 0 (and such a layer needs it): every step first
+        runs the net without gradients on the batch as given (the teacher), draws one
+        augmentation record per pair from (selfsup_seed, step number), and trains on the
+        augmented batch with the teacher's flow, carried through the same records, as the
+        target of the finest flow (train_step; DESIGN.md "Self-supervision")."""
         self.flow_net = flow_net
         self.optimizer = optimizer or KerasAdam(flow_net.store)
         self.loss_layer = loss_layer or LossLayer(
             warp_convention=getattr(flow_net, "warp_convention", "reference"))
         check_warp_conventions(flow_net, self.loss_layer)
+        check_selfsup(flow_net, self.loss_layer, selfsup)
+        self.selfsup = selfsup
+        self.selfsup_seed = int(selfsup_seed)
+        self.selfsup_enabled = selfsup is not None
+        self.last_selfsup = None
+        self._selfsup_step = 0
         if data_parallel is None:
             data_parallel = comm is not None or (torch.distributed.is_initialized() and
                                                  torch.distributed.get_world_size() > 1)
@@ -217,9 +256,54 @@ class Trainer:
                 comm = make_comm(kind, rank, world)
             self.reducer = GradBucketReducer(flow_net.store, comm=comm)
 
-    def train_step(self, batch_imgs, step_count=0, gt=None):
+    def teacher_pass(self, batch_imgs):
+        """The self-supervision teacher: the net's flows on ``batch_imgs`` without gradients
+        (on the doubled batch under occlusion="fb") and the level-0 occlusion mask of the first
+        B images (None under occlusion="none").  Weights, gradients, buffers and
+        ``store.version`` stay untouched.  Returns (finest flow (B, h, w, 2), mask)."""
+        nb = batch_imgs.shape[0]
+        occ = getattr(self.loss_layer, "occlusion", "none")
+        with torch.no_grad():
+            x = batch_imgs
+            if occ == "fb":
+                x = torch.cat([x, torch.cat([x[..., 3:], x[..., :3]], -1)], 0)
+            flows = self.flow_net(x)
+            mask = None
+            if occ != "none":
+                mask = ops.occlusion_masks(flows, occ, self.loss_layer.occlusion_alpha1,
+                                           self.loss_layer.occlusion_alpha2,
+                                           self.loss_layer.warp_convention)[0][:nb]
+            return flows[0][:nb].contiguous(), mask
+
+    def _selfsup_inputs(self, batch_imgs, records):
+        """Steps 1 and 2 of a self-supervised step: (augmented batch, (target, weight))."""
+        from .data_reader import sample_augment
+        nb, H, W = batch_imgs.shape[:3]
+        teacher, mask = self.teacher_pass(batch_imgs)
+        if records is None:
+            records = sample_augment(self.selfsup, nb, H, W, self.selfsup_seed,
+                                     self._selfsup_step)
+        self._selfsup_step += 1
+        rec = ops._records_dev(records, nb, batch_imgs.device)
+        student = ops.augment_batch(batch_imgs, rec)
+        target, weight = ops.transform_flow(teacher, rec, (H, W), mask)
+        self.last_selfsup = {"batch": student, "target": target, "weight": weight,
+                             "records": rec}
+        return student, (target, weight)
+
+    def train_step(self, batch_imgs, step_count=0, gt=None, selfsup_records=None):
         """``gt``: the batch's KITTI flow ground truth for a loss layer with
-        ``supervised_weight`` > 0 (what LossLayer's call takes); None otherwise."""
+        ``supervised_weight`` > 0 (what LossLayer's call takes); None otherwise.
+        ``selfsup_records``: with self-supervision on, this step's of_augment records (an
+        AUGMENT_DTYPE array or a CUDA uint8 tensor) in place of the seeded draw.  A
+        self-supervised step trains on the augmented batch and returns its flows;
+        ``last_selfsup`` then holds that batch, the target, the weight and the records.
+        ``selfsup_enabled = False`` makes the step the plain one."""
+        selfsup = None
+        if self.selfsup is not None and self.selfsup_enabled:
+            batch_imgs, selfsup = self._selfsup_inputs(batch_imgs, selfsup_records)
+        elif selfsup_records is not None:
+            raise ValueError("selfsup_records given, but self-supervision is off")
         store = self.flow_net.store
         store.zero_grad()
         if self.reducer is not None:
@@ -232,7 +316,9 @@ class Trainer:
             batch_imgs = torch.cat([batch_imgs,
                                     torch.cat([batch_imgs[..., 3:], batch_imgs[..., :3]], -1)], 0)
         flows = self.flow_net(batch_imgs)
-        if gt is not None:
+        if selfsup is not None or self.selfsup is not None:
+            loss_value = self._selfsup_loss(batch_imgs, flows, gt, selfsup)
+        elif gt is not None:
             loss_value = self.loss_layer(batch_imgs, flows, gt=gt)
         else:                           # as it always was (a custom loss takes two arguments)
             loss_value = self.loss_layer(batch_imgs, flows)
@@ -246,6 +332,20 @@ class Trainer:
         self.optimizer.apply_gradients(grad_scale=scale)
         # "fb": the caller sees the forward flows of the batch it passed
         return loss_value.detach(), [f.detach()[:nb] for f in flows]
+
+    def _selfsup_loss(self, batch_imgs, flows, gt, selfsup):
+        """The loss of a trainer built with self-supervision.  While it is switched off
+        (``selfsup_enabled`` False) the layer is called without a target and its
+        self-supervision term contributes nothing."""
+        layer = self.loss_layer
+        kw = {"gt": gt} if gt is not None else {}
+        if selfsup is not None:
+            return layer(batch_imgs, flows, selfsup=selfsup, **kw)
+        w, layer.selfsup_weight = layer.selfsup_weight, 0.0
+        try:
+            return layer(batch_imgs, flows, **kw)
+        finally:
+            layer.selfsup_weight = w
 
     def graphed(self, batch_imgs, warmup: int = 2, capture_ctx=None):
         """The step captured once as a HIP graph over a static input batch (train.py:47-48
@@ -287,6 +387,10 @@ class GraphedStep:
         if trainer.reducer is not None and getattr(trainer.reducer.comm, "kind", "") != "rccl":
             raise RuntimeError("graph capture needs the RCCL communicator (gloo collectives "
                                "cannot be captured)")
+        if getattr(trainer, "selfsup", None) is not None:
+            raise RuntimeError("graph capture does not take a self-supervised trainer "
+                               "(selfsup=...): the teacher pass and the per-step records are "
+                               "not captured; run train_step(batch) eagerly")
         if getattr(trainer.loss_layer, "supervised_weight", 0.0) != 0.0:
             raise RuntimeError("graph capture does not take a supervised loss layer "
                                "(supervised_weight > 0): the ground-truth buffer changes size "
@@ -452,14 +556,27 @@ def build_parser():
                          "robust fine-tuning penalty of the PWC-Net family")
     ap.add_argument("--supervised-eps", type=float, default=0.01,
                     help="eps of the supervised penalty, in native pixels")
+    ap.add_argument("--selfsup-weight", type=float, default=0.0, metavar="W",
+                    help="weight of the augmentation self-supervision term (0: off): the net's "
+                         "flow on the batch as read, carried through the --augment / --aug-* "
+                         "transform, is the target of its flow on the transformed batch; needs "
+                         "--warp-convention image")
+    ap.add_argument("--selfsup-q", type=float, default=0.4,
+                    help="exponent of the self-supervision penalty (|e|^2 + eps^2)^(q/2)")
+    ap.add_argument("--selfsup-eps", type=float, default=0.01,
+                    help="eps of the self-supervision penalty, in cells of the finest flow")
+    ap.add_argument("--selfsup-start-epoch", type=int, default=0, metavar="E",
+                    help="epochs before E train without the self-supervision term")
     ap.add_argument("--eval-kitti-flow", default=None, metavar="ROOT",
                     help="KITTI 2015 flow root: EPE and Fl-all against its ground truth after "
                          "every --eval-every epochs and at the end (needs --warp-convention image)")
     ap.add_argument("--eval-every", type=int, default=1, metavar="N",
                     help="epochs between evaluations (with --eval-kitti-flow)")
     g = ap.add_argument_group(
-        "augmentation (with --kitti only)", "seeded by --seed; both images of a pair get the "
-        "same draw; an --aug-* flag without --augment starts from no augmentation")
+        "augmentation (with --kitti, or with --selfsup-weight)", "seeded by --seed; both images "
+        "of a pair get the same draw; an --aug-* flag without --augment starts from no "
+        "augmentation; with --selfsup-weight the flags set the self-supervision transform, which "
+        "runs on the device, and the reader stays un-augmented")
     g.add_argument("--augment", action="store_true",
                    help="preset: zoom 1-1.3 with random crop position, horizontal flip p=0.5, "
                         "brightness +-0.1, contrast 0.8-1.2, saturation 0.8-1.2, per-channel "
@@ -521,6 +638,44 @@ def check_supervised_args(args):
             raise ValueError("--eval-every must be >= 1, got %d" % args.eval_every)
 
 
+def check_augment_args(args, augment):
+    """Where the augmentation flags (``augment``: their AugmentOpts, or None) apply: never with
+    --kitti-flow; with --kitti, where the reader augments; and with --selfsup-weight > 0, where
+    they set the self-supervision transform, which runs on the device on any batch.  ValueError
+    otherwise (main turns it into a parser error)."""
+    if augment is None:
+        return
+    if args.kitti_flow:
+        raise ValueError("--augment / --aug-* do not apply with --kitti-flow: a spatial "
+                         "augmentation would have to move the ground truth with the frame")
+    if not args.kitti and not args.selfsup_weight > 0:
+        raise ValueError("--augment / --aug-* apply only with --kitti: without it the driver "
+                         "trains on synthetic pairs, which are not augmented")
+
+
+def check_selfsup_args(args):
+    """--selfsup-weight > 0 needs --warp-convention image (an augmentation can only carry an
+    image displacement) and a transform to self-supervise with (--augment or an --aug-* flag);
+    --selfsup-q is in (0, 2], --selfsup-eps > 0, --selfsup-start-epoch >= 0.  ValueError
+    otherwise (main turns it into a parser error)."""
+    if args.selfsup_weight < 0:
+        raise ValueError("--selfsup-weight must be >= 0, got %r" % (args.selfsup_weight,))
+    if not 0 < args.selfsup_q <= 2:
+        raise ValueError("--selfsup-q must be in (0, 2], got %r" % (args.selfsup_q,))
+    if not args.selfsup_eps > 0:
+        raise ValueError("--selfsup-eps must be > 0, got %r" % (args.selfsup_eps,))
+    if args.selfsup_start_epoch < 0:
+        raise ValueError("--selfsup-start-epoch must be >= 0, got %d" % args.selfsup_start_epoch)
+    if args.selfsup_weight > 0:
+        if args.warp_convention != "image":
+            raise ValueError("--selfsup-weight > 0 needs --warp-convention image: a "
+                             "reference-convention flow is not an image displacement, an "
+                             "augmentation cannot carry it")
+        if augment_from_args(args) is None:
+            raise ValueError("--selfsup-weight > 0 needs a transform to self-supervise with: "
+                             "--augment or an --aug-* flag")
+
+
 def check_occlusion_args(args):
     """--occlusion masks are defined on image displacements, so anything but "none" needs
     --warp-convention image; the alphas are >= 0.  ValueError otherwise (main turns it into a
@@ -546,8 +701,9 @@ def header_record(args, augment=None):
     order2 = getattr(args, "smoothness_order", 1) == 2
     ssim = getattr(args, "ssim_weight", 0.0)
     sup = getattr(args, "supervised_weight", 0.0)
+    selfw = getattr(args, "selfsup_weight", 0.0)
     if not (args.smoothness_weight or args.edge_alpha or augment is not None or census or clip
-            or image or occ or order2 or ssim or sup):
+            or image or occ or order2 or ssim or sup or selfw):
         return None
     head = {"header": True, "smoothness_weight": args.smoothness_weight,
             "edge_alpha": args.edge_alpha}
@@ -559,6 +715,9 @@ def header_record(args, augment=None):
         head.update(supervised_weight=sup, supervised_q=args.supervised_q,
                     supervised_eps=args.supervised_eps, kitti_flow=args.kitti_flow,
                     kitti_flow_holdout=args.kitti_flow_holdout)
+    if selfw:                       # logs without self-supervision stay what they were
+        head["selfsup"] = {"weight": selfw, "q": args.selfsup_q, "eps": args.selfsup_eps,
+                           "start_epoch": args.selfsup_start_epoch}
     if census:
         head.update(census_weight=args.census_weight, census_radius=args.census_radius,
                     photometric_weight=args.photometric_weight)
@@ -584,17 +743,12 @@ def main(argv=None):
         augment = augment_from_args(args)
     except ValueError as e:
         ap.error(str(e))
-    if augment is not None and args.kitti_flow:
-        ap.error("--augment / --aug-* do not apply with --kitti-flow: a spatial augmentation "
-                 "would have to move the ground truth with the frame")
-    if augment is not None and not args.kitti:
-        ap.error("--augment / --aug-* apply only with --kitti: without it the driver trains on "
-                 "synthetic pairs, which are not augmented")
-
     try:
+        check_augment_args(args, augment)
         check_eval_args(args)
         check_occlusion_args(args)
         check_supervised_args(args)
+        check_selfsup_args(args)
     except ValueError as e:
         ap.error(str(e))
 
@@ -610,7 +764,9 @@ def main(argv=None):
                                ssim_weight=args.ssim_weight,
                                supervised_weight=args.supervised_weight,
                                supervised_q=args.supervised_q,
-                               supervised_eps=args.supervised_eps)
+                               supervised_eps=args.supervised_eps,
+                               selfsup_weight=args.selfsup_weight, selfsup_q=args.selfsup_q,
+                               selfsup_eps=args.selfsup_eps)
     except ValueError as e:
         ap.error(str(e))
     try:
@@ -627,7 +783,11 @@ def main(argv=None):
         net.summary()
     opt = KerasAdam(net.store, learning_rate=args.lr, global_clipnorm=args.clip_norm,
                     skip_nonfinite=args.skip_nonfinite, track_grad_norm=args.log_grad_norm)
-    trainer = Trainer(net, opt, loss_layer)
+    selfsup = args.selfsup_weight > 0
+    # with self-supervision the augmentation flags set its transform (on the device, seeded per
+    # rank like the reader); the reader then hands out the frames as they are
+    trainer = Trainer(net, opt, loss_layer, selfsup=augment if selfsup else None,
+                      selfsup_seed=args.seed + rank)
     log = open(args.log, "a") if (args.log and rank == 0) else None
     head = header_record(args, augment)
     if log and head is not None:
@@ -636,7 +796,8 @@ def main(argv=None):
     if args.kitti:
         from .data_reader import AsyncReader, ReaderOpts
         reader = AsyncReader(ReaderOpts(args.kitti, args.batch, args.height, args.width,
-                                        args.nworkers, seed=args.seed + rank, augment=augment))
+                                        args.nworkers, seed=args.seed + rank,
+                                        augment=None if selfsup else augment))
     labelled = None
     eval_frames = None
     if args.kitti_flow:
@@ -657,6 +818,8 @@ def main(argv=None):
     for epoch in range(args.epochs):
         if epoch == args.lr_drop_epoch:
             opt.learning_rate = args.lr * 0.1
+        if selfsup:
+            trainer.selfsup_enabled = epoch >= args.selfsup_start_epoch
         t0 = time.time()
         epoch_batches = iter(labelled) if labelled is not None else None
         for b in range(nbatches):
@@ -685,7 +848,10 @@ def main(argv=None):
                     log.write(json.dumps(rec) + "\n")
                 if args.display_dir and (b + 1) % 10 == 0:
                     from .drawing import display_training
-                    display_training(batch, flows, args.display_dir, step)
+                    shown = batch
+                    if selfsup and trainer.selfsup_enabled:      # the batch the flows belong to
+                        shown = trainer.last_selfsup["batch"]
+                    display_training(shown, flows, args.display_dir, step)
             step += 1
         if rank == 0:
             print("\nEpoch computed in %.3fs" % (time.time() - t0))
