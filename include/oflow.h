@@ -973,6 +973,48 @@ int of_supervised_fwd_multi(const float* const* flows, int n, int n_gt, const in
                             int64_t workspace_bytes, float* const* dsdfs, float* partials,
                             void* stream);
 
+/* Labelled augmentation (build-added): a raw ground-truth batch moved through the of_augment
+ * records that of_augment_pairs moves its frames through, so that a crop, zoom, flip or rotation
+ * of a labelled frame carries its sparse truth with it.
+ *   dev_gt_raw / host_descs / gt_bytes: of_flow_eval's ground-truth batch of n maps (host_descs
+ *   is required here); dev_params: n records in device memory, drawn for an img_h x img_w image
+ *   (record i serves map i).
+ *   dev_out: gt_bytes bytes of device memory, not dev_gt_raw.  It receives the n descriptors
+ *   unchanged (written by the kernel, on the stream) and, for each map, the augmented map of the
+ *   same h_i x w_i at the same offset: of_flow_eval and of_supervised_fwd_multi take it as it is,
+ *   with the same host_descs.  Every pixel of every map is written; the bytes between the maps
+ *   are not.
+ * Per output pixel (x, y) of map i (h = h_i, w = w_i), in fp32 in this order, no contraction,
+ * correctly rounded division (of_augment_pairs' convention; tests/gt_augment_ref.py restates it
+ * bit for bit):
+ *   xc = (x + 0.5) * img_w / w,  yc = (y + 0.5) * img_h / h      (the centre in record pixels);
+ *   u = (m0*xc + m1*yc) + m2,  v = (m3*xc + m4*yc) + m5;
+ *   xs = floor(u * w),  ys = floor(v * h): the source pixel the centre falls into.  A gather,
+ *   never a blend: bilinear taps would mix valid with invalid pixels and average vectors across
+ *   motion boundaries.
+ *   invalid if (xs, ys) lies outside the map, u or v is not finite, or the source pixel has
+ *   B == 0;  else g = ((R - 32768) / 64, (G - 32768) / 64), the devkit's decode of the source;
+ *   A = [[m0*img_w, m1*img_h*w/h], [m3*img_w*h/w, m4*img_h]]     (the map's linear part in native
+ *   pixels, of_flow_transform's A with the map in the place of the flow grid; products and
+ *   quotients left to right);  det = A00*A11 - A01*A10;
+ *   g' = A^-1 g = ((A11*g.x - A01*g.y) / det, (A00*g.y - A10*g.x) / det)     (a horizontal flip
+ *   negates g.x, a zoom z gives z*g);
+ *   q = rint(g' * 64 + 32768) per channel (round half to even);  invalid if either q lies
+ *   outside [0, 65535] or is not a number -- a clamped label would be a wrong label;
+ *   a valid pixel is written as (q.x, q.y, 1), an invalid one as (0, 0, 0).
+ * If |det| < 1e-12 (or det is not a number) the whole map is invalid.  No read leaves the source
+ * map for any record, finite or not.  A thread writes eight consecutive pixels as three 16-byte
+ * stores; a map at an even address that is not 16-byte aligned has a head of at most seven
+ * pixels before its first aligned group, heads and tails are written in 2-byte stores, a map at
+ * an odd address in byte stores.  No atomics, no allocation, no host sync; run-to-run bitwise
+ * equal.
+ * OF_EINVAL (and no launch) for a NULL pointer, dev_out == dev_gt_raw, either buffer not 16-byte
+ * aligned, n < 0 or > 65535, img_h or img_w < 1, a bad host descriptor (as of_flow_eval checks
+ * them; gt_bytes, the size of both buffers, must be > 0 when n > 0).  n == 0 launches nothing. */
+int of_gt_augment(const void* dev_gt_raw, const of_image_desc* host_descs, int64_t gt_bytes, int n,
+                  int img_h, int img_w, const of_augment* dev_params, void* dev_out,
+                  void* stream);
+
 /* ==== Augmentation self-supervision (build-added; the reference has none): the net's own flow
  * on the un-augmented batch (the teacher), carried through an of_augment record, is the target
  * of the flow it predicts on the augmented batch (the student).  Image convention only

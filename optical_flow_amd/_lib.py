@@ -237,6 +237,8 @@ PROTOTYPES = {
     "of_flow_transform": (I, [P, I, I, I, I, I, P, P, P, P, P]),
     "of_flow_distill_partials": (I, [I, I, I]),
     "of_flow_distill_fwd": (I, [P, P, P, I, I, I, F, F, F, P, P, P]),
+    # labelled augmentation: the ground-truth batch moved through the records
+    "of_gt_augment": (I, [P, P, I64, I, I, I, P, P, P]),
     "of_stem_bwd_fused_workspace": (SZ, [PD, I]),
     "of_stem_bwd_fused": (I, [PD, I, P, I, P, P, P, P, P, P, F, P, P, P, P, I, P, SZ, P]),
     # BatchNormalization in training mode (bn_mode="training")

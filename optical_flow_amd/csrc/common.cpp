@@ -22,6 +22,21 @@ int check_launch(const char* what) {
   return OF_OK;
 }
 
+int check_gt_descs(const char* who, const of_image_desc* descs, int n, int64_t gt_bytes) {
+  const int64_t header = round_up((int64_t)n * (int64_t)sizeof(of_image_desc), 256);
+  for (int i = 0; i < n; ++i) {
+    const of_image_desc& d = descs[i];
+    if (d.h <= 0 || d.w <= 0 || (int64_t)d.h * d.w >= INT32_MAX)
+      return fail(OF_EINVAL, std::string(who) + ": descriptor " + std::to_string(i) +
+                                 " has size " + std::to_string(d.h) + " x " + std::to_string(d.w));
+    const int64_t bytes = (int64_t)d.h * d.w * 6;
+    if (d.offset < header || (gt_bytes > 0 && d.offset > gt_bytes - bytes))
+      return fail(OF_EINVAL, std::string(who) + ": descriptor " + std::to_string(i) +
+                                 " lies outside the ground-truth buffer");
+  }
+  return OF_OK;
+}
+
 int device_cus() {
   static int cache[64] = {0};
   int dev = 0;

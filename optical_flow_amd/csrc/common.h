@@ -13,6 +13,11 @@ int fail(int code, const std::string& msg);
 // Check the launch that was just issued; converts a HIP error into OF_EHIP.
 int check_launch(const char* what);
 
+// The host descriptors of a raw ground-truth batch (of_flow_eval, include/oflow.h): h, w >= 1,
+// h * w < 2^31, the map past the 256-byte padded header and, when gt_bytes > 0, inside
+// gt_bytes.  OF_EINVAL with "<who>: descriptor i ..." otherwise.
+int check_gt_descs(const char* who, const of_image_desc* descs, int n, int64_t gt_bytes);
+
 // Conv launch timing (bench instrumentation), see of_timing_enable().
 bool timing_on();
 void timing_begin(hipStream_t s);

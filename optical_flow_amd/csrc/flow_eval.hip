@@ -192,19 +192,8 @@ int of_flow_eval(const float* flow, int n, int fh, int fw, const void* dev_gt_ra
   }
   OF_CHECK_ARG(npartials >= n && npartials % n == 0 && npartials / n <= kEvalMaxWgs,
                "flow eval: npartials is not of_flow_eval_partials(...)");
-  if (host_descs) {
-    const int64_t header = round_up((int64_t)n * (int64_t)sizeof(of_image_desc), 256);
-    for (int i = 0; i < n; ++i) {
-      const of_image_desc& d = host_descs[i];
-      if (d.h <= 0 || d.w <= 0 || (int64_t)d.h * d.w >= INT32_MAX)
-        return fail(OF_EINVAL, "flow eval: descriptor " + std::to_string(i) + " has size " +
-                                   std::to_string(d.h) + " x " + std::to_string(d.w));
-      const int64_t bytes = (int64_t)d.h * d.w * 6;
-      if (d.offset < header || (gt_bytes > 0 && d.offset > gt_bytes - bytes))
-        return fail(OF_EINVAL, "flow eval: descriptor " + std::to_string(i) +
-                                   " lies outside the ground-truth buffer");
-    }
-  }
+  if (host_descs)
+    if (const int st = check_gt_descs("flow eval", host_descs, n, gt_bytes)) return st;
   const int P = npartials / n;
   hipLaunchKernelGGL(flow_eval_kernel, dim3(P, n), dim3(kEvalThreads), 0, as_stream(stream),
                      flow, fh, fw, static_cast<const uint8_t*>(dev_gt_raw),

@@ -132,14 +132,25 @@ class KittiFlowReader:
     Every iteration is one epoch: the frames in a seeded shuffle of their own (``order``), the
     last short batch dropped.  Frames and maps are decoded ``nworkers`` at a time, up to two
     batches ahead, as evaluate() does; both go up by asynchronous copies from pinned staging.
-    No spatial augmentation: it would have to move the ground truth with the frame, so an
-    ``augment`` other than None raises ValueError."""
+    The reader's own ``augment`` (AsyncReader's keyword) would move the frames and leave the
+    ground truth behind, so anything but None raises ValueError.  ``label_augment`` (an
+    AugmentOpts) moves both: batch k of epoch e draws ``records(e, k)``, the frames go through
+    of_augment_pairs in place of of_preprocess_pairs and the maps through of_gt_augment with the
+    same records (ops.augment_gt; DESIGN.md "Labelled augmentation").  With None, the default,
+    nothing changes and neither kernel is launched."""
 
     def __init__(self, frames_or_root, batch_size: int, img_height: int, img_width: int,
-                 gt: str = "occ", nworkers: int = 6, seed: int = 0, augment=None):
+                 gt: str = "occ", nworkers: int = 6, seed: int = 0, augment=None,
+                 label_augment=None):
         if augment is not None:
             raise ValueError("labelled KITTI flow frames are not augmented (AugmentOpts given): a "
                              "crop, zoom or flip would have to move the ground truth with it")
+        if label_augment is not None:
+            from .data_reader import AugmentOpts
+            if not isinstance(label_augment, AugmentOpts):
+                raise TypeError("label_augment must be an AugmentOpts or None, got %r"
+                                % (type(label_augment),))
+        self.label_augment = label_augment
         if isinstance(frames_or_root, (str, os.PathLike)):
             frames = list_kitti_flow(frames_or_root, gt)
         else:
@@ -162,6 +173,19 @@ class KittiFlowReader:
         epoch), cut to whole batches."""
         perm = np.random.default_rng([self.seed, int(epoch)]).permutation(len(self.frames))
         return [int(i) for i in perm[:self.nbatches * self.batch_size]]
+
+    def records(self, epoch: int, k: int):
+        """The of_augment records of batch ``k`` of ``epoch`` (label_augment only):
+        sample_augment seeded by (seed, epoch * nbatches + k), one record per frame, shared by
+        the frame's two images and its ground-truth map."""
+        if self.label_augment is None:
+            raise ValueError("records() needs a reader built with label_augment")
+        if not 0 <= int(k) < self.nbatches or int(epoch) < 0:
+            raise ValueError("batch %r of epoch %r: the reader has %d batches per epoch"
+                             % (k, epoch, self.nbatches))
+        from .data_reader import sample_augment
+        return sample_augment(self.label_augment, self.batch_size, self.height, self.width,
+                              self.seed, int(epoch) * self.nbatches + int(k))
 
     def host_batches(self, epoch: int):
         """The epoch's batches on the host: (pairs, maps, indices) per batch -- BGR uint8 frame
@@ -191,13 +215,27 @@ class KittiFlowReader:
     def __iter__(self):
         from .data_reader import _pack_raw
         epoch, self.epoch = self.epoch, self.epoch + 1
-        for pairs, maps, _ in self.host_batches(epoch):
+        for k, (pairs, maps, _) in enumerate(self.host_batches(epoch)):
             dev = _upload(_pack_raw(pairs))
             batch = torch.empty((len(pairs), self.height, self.width, 6), device="cuda")
+            if self.label_augment is not None:
+                yield self._augmented(epoch, k, dev, batch, maps)
+                continue
             call("of_preprocess_pairs", C.c_void_p(dev.data_ptr()), len(pairs), self.height,
                  self.width, C.c_void_p(batch.data_ptr()), _stream())
             raw, descs = pack_gt_raw(maps)
             yield batch, _upload(raw), descs
+
+    def _augmented(self, epoch, k, dev, batch, maps):
+        """One batch of the label_augment path: the raw frames ``dev`` into ``batch`` through
+        records(epoch, k), and the maps through the same records."""
+        from . import ops
+        rec = _upload(self.records(epoch, k).view(np.uint8))
+        call("of_augment_pairs", C.c_void_p(dev.data_ptr()), batch.shape[0], self.height,
+             self.width, C.c_void_p(rec.data_ptr()), C.c_void_p(batch.data_ptr()), _stream())
+        raw, descs = pack_gt_raw(maps)
+        gt_raw, descs = ops.augment_gt((_upload(raw), descs), rec, (self.height, self.width))
+        return batch, gt_raw, descs
 
 
 # ---- device ops -------------------------------------------------------------------------------

@@ -2462,6 +2462,32 @@ def transform_flow(flow, records, img_hw, mask=None):
     return target, weight
 
 
+def augment_gt(gt, records, img_hw):
+    """of_gt_augment (include/oflow.h): KITTI ground truth carried through one of_augment record
+    per map -> (CUDA uint8 buffer, host descriptors), the form flow_metrics, supervised_flow_loss
+    and Trainer.train_step(gt=...) take.  ``gt`` is what _gt_handle accepts (a list of (h, w, 3)
+    uint16 maps, pack_gt_raw's buffer, or the pair (buffer, descriptors)); ``records`` what
+    _records_dev accepts, drawn for an image of ``img_hw`` = (H, W) -- the records the maps'
+    frames go through in of_augment_pairs.  Each output pixel takes the source pixel its centre
+    falls into (no blend of valid and invalid pixels), its vector mapped through the inverse of
+    the record's linear part; sizes, offsets and descriptors are the input's.  No autograd: the
+    ground truth is data (DESIGN.md "Labelled augmentation")."""
+    import numpy as np
+    from .data_reader import AUGMENT_DTYPE
+    if isinstance(records, torch.Tensor):
+        nrec = records.numel() // AUGMENT_DTYPE.itemsize
+    else:
+        nrec = np.asarray(records).size
+    raw, descs = _gt_handle(gt, nrec)
+    n = len(descs)
+    rec = _records_dev(records, n, raw.device)
+    raw = raw.contiguous()
+    out = torch.empty_like(raw)
+    call("of_gt_augment", _ptr(raw), descs.ctypes.data_as(C.c_void_p), raw.numel(), n,
+         int(img_hw[0]), int(img_hw[1]), _ptr(rec), _ptr(out), _stream())
+    return out, descs
+
+
 def _self_fwd(f0, target, weight, q, eps, coef, want_grad):
     """of_flow_distill_fwd on the finest flow (the self-supervision term, include/oflow.h):
     (partials, plane).  The first target.shape[0] images are scored; the partials sum to coef *

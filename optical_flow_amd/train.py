@@ -12,7 +12,8 @@ KITTI each rank reads its own seeded shuffle.  ``--augment`` (KITTI only) switch
 seeded GPU augmentation of data_reader.AugmentOpts: random zoom / crop, flip, colour jitter.
 ``--kitti-flow ROOT`` reads the labelled frames of a KITTI 2015 flow tree instead and, with
 ``--supervised-weight`` > 0, fine-tunes on their sparse ground truth (evaluate.KittiFlowReader;
-``--kitti-flow-holdout K`` keeps every K-th frame for evaluation).
+``--kitti-flow-holdout K`` keeps every K-th frame for evaluation); ``--kitti-flow-augment`` /
+``--kitti-flow-aug-*`` augment those frames and carry their ground truth along (of_gt_augment).
 ``--selfsup-weight W`` > 0 adds augmentation self-supervision (the teacher's flow on the batch
 as read is the target on the batch moved through the ``--augment`` / ``--aug-*`` transform, on
 the device, so it also runs without ``--kitti``; ``--selfsup-start-epoch E`` starts it later).
@@ -24,7 +25,7 @@ Run:  python -m optical_flow_amd.train --height 384 --width 512 --batch 8 --step
       python -m optical_flow_amd.train --kitti /data/kitti_raw --epochs 20 --augment
       python -m optical_flow_amd.train --kitti-flow /data/kitti_flow --warp-convention image \\
           --photometric-weight 0 --supervised-weight 1 --supervised-q 0.4 \\
-          --kitti-flow-holdout 5 --pretrained ckpt/flow_net_19/weights
+          --kitti-flow-holdout 5 --pretrained ckpt/flow_net_19/weights --kitti-flow-augment
       python -m optical_flow_amd.train --kitti /data/kitti_raw --warp-convention image \\
           --occlusion fb --census-weight 1 --selfsup-weight 0.3 --selfsup-start-epoch 5 --augment
 """
@@ -492,6 +493,41 @@ def augment_from_args(args):
     return AugmentOpts(**kw)
 
 
+def kitti_flow_augment_from_args(args):
+    """The AugmentOpts of --kitti-flow-augment / --kitti-flow-aug-*, which augment the labelled
+    frames together with their ground truth: None without any of them; --kitti-flow-augment is
+    AUGMENT_PRESET; each override replaces one field of the preset, or of the identity without
+    it.  ValueError (AugmentOpts) for a bad value."""
+    from .data_reader import AugmentOpts
+    over = {}
+    if args.kitti_flow_aug_zoom_max is not None:
+        over["zoom"] = (1.0, args.kitti_flow_aug_zoom_max)
+    if args.kitti_flow_aug_hflip is not None:
+        over["hflip_prob"] = args.kitti_flow_aug_hflip
+    if args.kitti_flow_aug_rotate is not None:
+        over["rotate_deg"] = args.kitti_flow_aug_rotate
+    if not args.kitti_flow_augment and not over:
+        return None
+    kw = dict(AUGMENT_PRESET) if args.kitti_flow_augment else {}
+    kw.update(over)
+    return AugmentOpts(**kw)
+
+
+def check_kitti_flow_augment_args(args, label_augment):
+    """--kitti-flow-augment / --kitti-flow-aug-* (``label_augment``: their AugmentOpts, or None)
+    need --kitti-flow, whose frames they augment, and --warp-convention image: the ground truth
+    they carry is an image displacement.  ValueError otherwise (main turns it into a parser
+    error)."""
+    if label_augment is None:
+        return
+    if not args.kitti_flow:
+        raise ValueError("--kitti-flow-augment / --kitti-flow-aug-* need --kitti-flow: they "
+                         "augment its labelled frames and ground truth")
+    if args.warp_convention != "image":
+        raise ValueError("--kitti-flow-augment / --kitti-flow-aug-* need --warp-convention image: "
+                         "the ground truth they carry is an image displacement")
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--height", type=int, default=192)       # train.py:15
@@ -595,6 +631,20 @@ def build_parser():
                    help="saturation factor uniform in [1-A, 1+A]")
     g.add_argument("--aug-color-gain", type=float, default=None, metavar="A",
                    help="per-channel gain uniform in [1-A, 1+A]")
+    g = ap.add_argument_group(
+        "augmentation of the labelled frames (with --kitti-flow and --warp-convention image)",
+        "seeded by --seed; a frame's two images and its ground-truth map get the same draw, the "
+        "map by a nearest-pixel gather with its vectors mapped through the crop; a "
+        "--kitti-flow-aug-* flag without --kitti-flow-augment starts from no augmentation; "
+        "held-out and evaluation frames are never augmented")
+    g.add_argument("--kitti-flow-augment", action="store_true",
+                   help="the --augment preset on the labelled frames and their ground truth")
+    g.add_argument("--kitti-flow-aug-zoom-max", type=float, default=None, metavar="Z",
+                   help="zoom uniform in [1, Z]; the crop is 1/zoom of the frame per axis")
+    g.add_argument("--kitti-flow-aug-hflip", type=float, default=None, metavar="P",
+                   help="probability of a horizontal flip")
+    g.add_argument("--kitti-flow-aug-rotate", type=float, default=None, metavar="DEG",
+                   help="rotation uniform in +-DEG about the image centre (preset: 0)")
     return ap
 
 
@@ -689,10 +739,11 @@ def check_occlusion_args(args):
                          % args.occlusion)
 
 
-def header_record(args, augment=None):
+def header_record(args, augment=None, label_augment=None):
     """The step log's header record (no "step" key) for a run with any non-default loss,
     augmentation, clipping or warp-convention option; None for a default run, whose log holds
-    step records only."""
+    step records only.  ``label_augment``: the AugmentOpts of the labelled frames
+    (kitti_flow_augment_from_args), recorded as "kitti_flow_augment" when set."""
     census = (args.census_weight != 0.0 or args.census_radius != 3 or
               args.photometric_weight != 1.0)
     clip = args.clip_norm is not None or args.skip_nonfinite or args.log_grad_norm
@@ -703,7 +754,7 @@ def header_record(args, augment=None):
     sup = getattr(args, "supervised_weight", 0.0)
     selfw = getattr(args, "selfsup_weight", 0.0)
     if not (args.smoothness_weight or args.edge_alpha or augment is not None or census or clip
-            or image or occ or order2 or ssim or sup or selfw):
+            or image or occ or order2 or ssim or sup or selfw or label_augment is not None):
         return None
     head = {"header": True, "smoothness_weight": args.smoothness_weight,
             "edge_alpha": args.edge_alpha}
@@ -723,6 +774,8 @@ def header_record(args, augment=None):
                     photometric_weight=args.photometric_weight)
     if augment is not None:
         head["augment"] = augment.as_dict()
+    if label_augment is not None:   # logs without labelled augmentation stay what they were
+        head["kitti_flow_augment"] = label_augment.as_dict()
     if clip:
         head.update(clip_norm=args.clip_norm, skip_nonfinite=args.skip_nonfinite,
                     log_grad_norm=args.log_grad_norm)
@@ -741,10 +794,12 @@ def main(argv=None):
     args = ap.parse_args(argv)
     try:
         augment = augment_from_args(args)
+        label_augment = kitti_flow_augment_from_args(args)
     except ValueError as e:
         ap.error(str(e))
     try:
         check_augment_args(args, augment)
+        check_kitti_flow_augment_args(args, label_augment)
         check_eval_args(args)
         check_occlusion_args(args)
         check_supervised_args(args)
@@ -789,7 +844,7 @@ def main(argv=None):
     trainer = Trainer(net, opt, loss_layer, selfsup=augment if selfsup else None,
                       selfsup_seed=args.seed + rank)
     log = open(args.log, "a") if (args.log and rank == 0) else None
-    head = header_record(args, augment)
+    head = header_record(args, augment, label_augment)
     if log and head is not None:
         log.write(json.dumps(head) + "\n")
     reader = None
@@ -808,7 +863,8 @@ def main(argv=None):
             if rank == 0:
                 eval_frames = held
         labelled = KittiFlowReader(frames, args.batch, args.height, args.width,
-                                   nworkers=args.nworkers, seed=args.seed + rank)
+                                   nworkers=args.nworkers, seed=args.seed + rank,
+                                   label_augment=label_augment)
     nbatches = (reader.nbatches if reader is not None else
                 labelled.nbatches if labelled is not None else args.steps)
     if args.eval_kitti_flow is not None and rank == 0:
