@@ -513,6 +513,34 @@ int of_occ_mask_multi(const float* const* flows, int n, int pair_stride, const i
                       const int* ws, int levels, int mode, float alpha1, const float* alpha2s,
                       float* const* masks, void* stream);
 
+/* Range-map occlusion (Wang et al., CVPR 2018; image convention only), every level in one
+ * launch per kernel.  flows[l] is (n,hs[l],ws[l],2), 8-byte aligned, n == 2 * pair_stride:
+ * images [0,B) hold the forward flows and [B,2B) those of the same pairs exchanged; image b's
+ * partner is (b + pair_stride) % n.  Every pixel (i,j) of the partner's flow g is moved to
+ * x = j + g0, y = i + g1 (fp32, the OF_WARP_IMAGE sample point) and splatted bilinearly on the
+ * four pixels (floor(y) + {0,1}, floor(x) + {0,1}) of image b with the weights (1 - fy | fy) *
+ * (1 - fx | fx); a tap outside the frame is dropped (not clamped), a non-finite point
+ * contributes nothing.  With R[b,p] the sum of the tap weights that land on p:
+ *   ranges[l][b,p] = R[b,p]                                     (>= 0, unclamped)
+ *   masks[l][b,p]  = border(flows[l][b,p]) * min(1, R[b,p])     (border: OF_OCC_BORDER's test)
+ * both dense (n,hs[l],ws[l]) floats, every element written.  `ranges` or `masks` may be NULL,
+ * and so may single entries: those are not written; at least one entry must be given.
+ * Each tap weight is rounded to a multiple of 2^-24 and summed in a 64-bit integer per
+ * destination pixel (no float atomics), so the result is bitwise reproducible; R is within
+ * 2^-25 per landed tap of the sum of the fp32 weights.  `workspace`: of_occ_range_ws_bytes
+ * bytes (8 per pixel), 8-byte aligned, overwritten.  A constant of the loss: nothing
+ * differentiates through it.  No allocation, no host sync.  OF_EINVAL (nothing launched,
+ * outputs and workspace untouched) for levels outside 1..8, n < 2 or n != 2 * pair_stride, h or
+ * w < 1, a level of >= 2^40 pixels, a NULL or not 8-byte aligned flow or workspace, a workspace
+ * smaller than of_occ_range_ws_bytes, no output.  of_occ_range_ws_bytes is 0 for arguments
+ * the entry rejects.  OF_OCC_RANGE names the estimator beside OF_OCC_BORDER / OF_OCC_FB;
+ * of_occ_mask_multi does not take it. */
+#define OF_OCC_RANGE 3
+size_t of_occ_range_ws_bytes(int n, const int* hs, const int* ws, int levels);
+int of_occ_range_multi(const float* const* flows, int n, int pair_stride, const int* hs,
+                       const int* ws, int levels, void* workspace, size_t workspace_bytes,
+                       float* const* ranges, float* const* masks, void* stream);
+
 /* The multi-level data terms with a per-pixel weight (an occlusion mask, or any non-negative
  * float): weights[l] is dense (n,hs[l],ws[l]); a NULL `weights`, or a NULL weights[l], is
  * weight 1 for every pixel (of that level).  The weights are constants.  Everything else is

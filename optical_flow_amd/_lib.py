@@ -19,6 +19,7 @@ OF_REDUCE_SUM, OF_REDUCE_AVG = 0, 1         # of_comm_allreduce_ex_async op
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 WARP_REFERENCE, WARP_IMAGE = 0, 1           # OF_WARP_REFERENCE / OF_WARP_IMAGE of the _cv entries
 OCC_BORDER, OCC_FB = 1, 2                   # OF_OCC_BORDER / OF_OCC_FB of of_occ_mask_multi
+OCC_RANGE = 3                               # OF_OCC_RANGE: of_occ_range_multi's estimator
 
 
 class B16iIO(C.Structure):
@@ -212,6 +213,11 @@ PROTOTYPES = {
     # forms with the per-level weights after the flows
     "of_occ_mask_multi": (I, [C.POINTER(P), I, I, C.POINTER(I), C.POINTER(I), I, I, F,
                               C.POINTER(F), C.POINTER(P), P]),
+    # range-map occlusion (OCC_RANGE): workspace bytes; flows, n, pair stride, hs, ws, levels,
+    # workspace, its bytes, ranges, masks, stream
+    "of_occ_range_ws_bytes": (SZ, [I, C.POINTER(I), C.POINTER(I), I]),
+    "of_occ_range_multi": (I, [C.POINTER(P), I, I, C.POINTER(I), C.POINTER(I), I, P, SZ,
+                               C.POINTER(P), C.POINTER(P), P]),
     "of_photo_l1_fwd_multi_w": (I, [C.POINTER(P), C.POINTER(P), C.POINTER(P), I, C.POINTER(I),
                                     C.POINTER(I), I, P, I, P]),
     "of_photo_l1_bwd_multi_w": (I, [C.POINTER(P), C.POINTER(P), C.POINTER(P), I, C.POINTER(I),

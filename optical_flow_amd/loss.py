@@ -46,6 +46,11 @@ class LossLayer:
     [pairs ; the same pairs with the two images exchanged] (Trainer.train_step forms it).  The
     masks are computed from the flows as constants (ops.occlusion_masks; DESIGN.md "Occlusion
     masks"); the means stay over all pixels and the smoothness term is not masked.
+    "range" (the doubled batch again, wherever "fb" needs it) weighs the data terms by the soft
+    range-map mask of Wang et al. (CVPR 2018): every pixel of image 2 is moved by the backward
+    flow and splatted bilinearly into image 1, and a pixel's weight is min(1, what landed on it)
+    times the border mask, a float in [0, 1] with no thresholds (``occlusion_alpha1`` and
+    ``occlusion_alpha2`` play no part; ops.range_map, DESIGN.md "Range-map occlusion").
 
     ``supervised_weight`` > 0 (build-added, image convention only) adds that weight times the
     supervised term against KITTI flow ground truth, passed to the call as ``gt`` (a list of
@@ -55,9 +60,9 @@ class LossLayer:
     pixels, is averaged over an image's valid pixels, then over the images that have one, then
     over the scales with ``supervised_level_weights`` (default 1 / scales each)
     (ops.supervised_flow_loss; DESIGN.md "Supervised term").  With it the three unsupervised
-    data weights may all be 0 (pure fine-tuning).  With ``occlusion="fb"`` it scores the
-    forward pairs only (the first half of the doubled batch); the occlusion masks do not weigh
-    it.
+    data weights may all be 0 (pure fine-tuning).  With ``occlusion="fb"`` or ``"range"`` it
+    scores the forward pairs only (the first half of the doubled batch); the occlusion masks do
+    not weigh it.
 
     ``selfsup_weight`` > 0 (build-added, image convention only) adds that weight times the
     self-supervision term: the finest flow against a target that ops.transform_flow carried over
@@ -74,8 +79,9 @@ class LossLayer:
                  selfsup_weight=0.0, selfsup_q=0.4, selfsup_eps=0.01, smoothness_order=1):
         ops.warp_convention(warp_convention)
         self.warp_convention = warp_convention
-        if occlusion not in ("none", "border", "fb"):
-            raise ValueError("occlusion must be 'none', 'border' or 'fb', got %r" % (occlusion,))
+        if occlusion not in ("none", "border", "fb", "range"):
+            raise ValueError("occlusion must be 'none', 'border', 'fb' or 'range', got %r"
+                             % (occlusion,))
         if not occlusion_alpha1 >= 0:
             raise ValueError("occlusion_alpha1 must be >= 0, got %r" % (occlusion_alpha1,))
         if not occlusion_alpha2 >= 0:
@@ -187,10 +193,10 @@ class LossLayer:
                                             self.smoothness_weight, self.edge_alpha,
                                             self.smoothness_eps, self.warp_convention, **order)
         if self.occlusion != "none":
-            if self.occlusion == "fb" and batch_imgs.shape[0] % 2:
-                raise ValueError("occlusion='fb' scores the doubled batch [pairs ; swapped "
+            if ops.needs_swapped_pairs(self.occlusion) and batch_imgs.shape[0] % 2:
+                raise ValueError("occlusion=%r scores the doubled batch [pairs ; swapped "
                                  "pairs]: an even number of images, got %d"
-                                 % batch_imgs.shape[0])
+                                 % (self.occlusion, batch_imgs.shape[0]))
             masks = ops.occlusion_masks([f.detach() for f in flows], self.occlusion,
                                         self.occlusion_alpha1, self.occlusion_alpha2,
                                         self.warp_convention)
@@ -212,7 +218,7 @@ class LossLayer:
                                     self.smoothness_eps, self.warp_convention, **order)
 
     def _forward_gt(self, gt, nb):
-        """The ground truth as ops takes it; with occlusion="fb" it belongs to the forward
-        pairs, the first half of the doubled batch."""
-        n = nb // 2 if self.occlusion == "fb" else nb
+        """The ground truth as ops takes it; with occlusion="fb" or "range" it belongs to the
+        forward pairs, the first half of the doubled batch."""
+        n = nb // 2 if ops.needs_swapped_pairs(self.occlusion) else nb
         return ops._gt_handle(gt, n)

@@ -2891,7 +2891,44 @@ def selfsup_flow_loss(flow, target, weight, q=0.4, eps=0.01):
 
 
 # ============================================================== occlusion masks =====
-OCCLUSION_MODES = {"border": _lib.OCC_BORDER, "fb": _lib.OCC_FB}
+OCCLUSION_MODES = {"border": _lib.OCC_BORDER, "fb": _lib.OCC_FB, "range": _lib.OCC_RANGE}
+
+
+def needs_swapped_pairs(mode):
+    """Whether occlusion ``mode`` reads the partner's flow, i.e. is computed on the doubled
+    batch [pairs ; the same pairs with the two images exchanged]."""
+    return mode in ("fb", "range")
+
+
+def _occ_range(flows, want_range, want_mask):
+    """of_occ_range_multi on a doubled batch: (ranges or None, masks or None), per level."""
+    ns = len(flows)
+    if not 1 <= ns <= 8:
+        raise ValueError("the range map takes 1..8 levels, got %d" % ns)
+    n = flows[0].shape[0]
+    if n < 2 or n % 2:
+        raise ValueError("occlusion mode 'range' needs the doubled batch [forward ; swapped]: "
+                         "an even number of images, got %d" % n)
+    _check_dev(*flows)
+    fl = [f.detach().contiguous() for f in flows]
+    hs, ws = _arr(C.c_int, [f.shape[1] for f in fl]), _arr(C.c_int, [f.shape[2] for f in fl])
+    nbytes = _lib.lib().of_occ_range_ws_bytes(n, hs, ws, ns)
+    acc = torch.empty(nbytes // 8, dtype=torch.int64, device=fl[0].device)
+    outs = [[torch.empty(f.shape[:3], device=f.device) for f in fl] if want else None
+            for want in (want_range, want_mask)]
+    call("of_occ_range_multi", _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, n // 2, hs, ws,
+         ns, acc.data_ptr(), nbytes,
+         *[_arr(C.c_void_p, [t.data_ptr() for t in o]) if o is not None else None for o in outs],
+         _stream())
+    return outs
+
+
+def range_map(flows):
+    """Per level the (n,h,w) float range map R of a doubled batch [forward flows ; flows of the
+    same pairs swapped]: R[b,p] is the bilinear weight that the pixels of image b's partner,
+    each moved by the partner's flow, put on pixel p; unclamped, >= 0 (include/oflow.h,
+    of_occ_range_multi; DESIGN.md "Range-map occlusion").  No autograd."""
+    return _occ_range(flows, True, False)[0]
 
 
 def occlusion_masks(flows, mode, alpha1=0.01, alpha2=0.5, convention="image"):
@@ -2904,14 +2941,19 @@ def occlusion_masks(flows, mode, alpha1=0.01, alpha2=0.5, convention="image"):
     pair_stride = n // 2); 1 iff inside the frame and |f + g~|^2 <= alpha1 (|f|^2 + |g~|^2) +
     alpha2_s, g~ the partner's flow sampled at the sample point.  ``alpha2`` is in squared
     full-resolution pixels: level s (1/2^(s+1) of the resolution, flows in its own pixels)
-    gets alpha2 / 4^(s+1).  Image convention only: a reference-convention flow is not a
-    displacement."""
+    gets alpha2 / 4^(s+1).
+    ``mode`` "range": the same doubled batch; a soft weight in [0, 1], the border mask times
+    min(1, R) with R the range map (range_map; of_occ_range_multi).  It has no thresholds: the
+    alphas are accepted and ignored.
+    Image convention only: a reference-convention flow is not a displacement."""
     if mode not in OCCLUSION_MODES:
         raise ValueError("occlusion mode must be one of %s, got %r"
                          % (sorted(OCCLUSION_MODES), mode))
     if warp_convention(convention) != _lib.WARP_IMAGE:
         raise ValueError("occlusion masks need the image warp convention: a %r-convention flow "
                          "is not a displacement" % (convention,))
+    if mode == "range":
+        return _occ_range(flows, False, True)[1]
     if not alpha1 >= 0 or not alpha2 >= 0:
         raise ValueError("occlusion alphas must be >= 0, got %r and %r" % (alpha1, alpha2))
     ns = len(flows)

@@ -16,7 +16,8 @@ seeded GPU augmentation of data_reader.AugmentOpts: random zoom / crop, flip, co
 ``--kitti-flow-aug-*`` augment those frames and carry their ground truth along (of_gt_augment).
 ``--selfsup-weight W`` > 0 adds augmentation self-supervision (the teacher's flow on the batch
 as read is the target on the batch moved through the ``--augment`` / ``--aug-*`` transform, on
-the device, so it also runs without ``--kitti``; ``--selfsup-start-epoch E`` starts it later).
+the device, so it also runs without ``--kitti``; ``--selfsup-start-epoch E`` starts it later;
+with ``--occlusion range`` the teacher's weight is the soft range-map mask, carried bilinearly).
 ``--clip-norm C`` / ``--skip-nonfinite`` / ``--log-grad-norm`` switch on KerasAdam's global-norm
 clipping, its non-finite update guard and the per-step gradient norm in the step log.
 
@@ -259,14 +260,15 @@ class Trainer:
 
     def teacher_pass(self, batch_imgs):
         """The self-supervision teacher: the net's flows on ``batch_imgs`` without gradients
-        (on the doubled batch under occlusion="fb") and the level-0 occlusion mask of the first
-        B images (None under occlusion="none").  Weights, gradients, buffers and
-        ``store.version`` stay untouched.  Returns (finest flow (B, h, w, 2), mask)."""
+        (on the doubled batch under occlusion="fb" or "range") and the level-0 occlusion mask
+        of the first B images (None under occlusion="none"; under "range" the soft weight,
+        which transform_flow carries bilinearly like any mask).  Weights, gradients, buffers
+        and ``store.version`` stay untouched.  Returns (finest flow (B, h, w, 2), mask)."""
         nb = batch_imgs.shape[0]
         occ = getattr(self.loss_layer, "occlusion", "none")
         with torch.no_grad():
             x = batch_imgs
-            if occ == "fb":
+            if ops.needs_swapped_pairs(occ):
                 x = torch.cat([x, torch.cat([x[..., 3:], x[..., :3]], -1)], 0)
             flows = self.flow_net(x)
             mask = None
@@ -310,10 +312,10 @@ class Trainer:
         if self.reducer is not None:
             self.reducer.begin()
         nb = batch_imgs.shape[0]
-        if getattr(self.loss_layer, "occlusion", "none") == "fb":
-            # forward-backward check: the net also sees every pair with its images exchanged
-            # ([batch ; swapped], device-only ops: the step still captures); the loss is the
-            # mean over both directions
+        if ops.needs_swapped_pairs(getattr(self.loss_layer, "occlusion", "none")):
+            # forward-backward check, range map: the net also sees every pair with its images
+            # exchanged ([batch ; swapped], device-only ops: the step still captures); the loss
+            # is the mean over both directions
             batch_imgs = torch.cat([batch_imgs,
                                     torch.cat([batch_imgs[..., 3:], batch_imgs[..., :3]], -1)], 0)
         flows = self.flow_net(batch_imgs)
@@ -331,7 +333,7 @@ class Trainer:
             bufs = store.buffers if getattr(self.flow_net, "bn_mode", "") == "training" else None
             scale = self.reducer.finish(buffers=bufs)
         self.optimizer.apply_gradients(grad_scale=scale)
-        # "fb": the caller sees the forward flows of the batch it passed
+        # "fb", "range": the caller sees the forward flows of the batch it passed
         return loss_value.detach(), [f.detach()[:nb] for f in flows]
 
     def _selfsup_loss(self, batch_imgs, flows, gt, selfsup):
@@ -569,10 +571,12 @@ def build_parser():
     ap.add_argument("--warp-convention", default="reference", choices=("reference", "image"),
                     help="the grid every warp adds the flow to: the reference's transposed grid "
                          "(default) or image coordinates (flow = (x, y) displacement)")
-    ap.add_argument("--occlusion", default="none", choices=("none", "border", "fb"),
+    ap.add_argument("--occlusion", default="none", choices=("none", "border", "fb", "range"),
                     help="mask the data terms where the sample leaves the frame (border) or "
                          "also fails the forward-backward check (fb: every step runs the "
-                         "pairs both ways); needs --warp-convention image")
+                         "pairs both ways), or weigh them by the soft range map of the "
+                         "backward flow (range: both ways too, no thresholds, the alphas play "
+                         "no part); needs --warp-convention image")
     ap.add_argument("--occ-alpha1", type=float, default=0.01,
                     help="relative tolerance of the forward-backward check")
     ap.add_argument("--occ-alpha2", type=float, default=0.5,

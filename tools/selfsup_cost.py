@@ -76,7 +76,7 @@ def main():
     ap.add_argument("--height", type=int, default=384)
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--batch", type=int, default=8)
-    ap.add_argument("--occlusion", default="none", choices=("none", "border", "fb"))
+    ap.add_argument("--occlusion", default="none", choices=("none", "border", "fb", "range"))
     ap.add_argument("--kernel-stats", default=None, metavar="FILE",
                     help="a rocprofv3 kernel_stats csv: only set the new kernels' times "
                          "against their bytes, no GPU run")
