@@ -9,10 +9,11 @@
 // (tau odd, phi even), so dC/du[q] = (2/K) sum_o phi'(e[q,o]) tau'(u[q+o] - u[q]) needs no
 // cross-pixel gather: the same loop forms it, and the kernel writes dC/d(flow) = dC/du *
 // du/d(flow) as a dense plane.  One partial per workgroup (wave shuffles, then LDS), no
-// atomics: run-to-run bitwise equal.  Backward: pixelwise scale of the plane into d(flow).
+// atomics: run-to-run bitwise equal.  Backward: pixelwise scale of the plane into d(flow)
+// (plane_scale_multi, loss_levels.h).
 #include <algorithm>
 
-#include "common.h"
+#include "loss_levels.h"
 #include "warp_tap.h"
 
 namespace oflow {
@@ -23,19 +24,12 @@ constexpr float CN_S = 255.f;        // images are u8/255 - mean: c_t on the 8-b
 constexpr float CN_CT = 0.81f;       // soft ternary sign
 constexpr float CN_CD = 0.1f;        // soft Hamming contribution
 
-// Level l's workgroups are [beg[l], beg[l+1]) in the forward: image-major, then tile row,
-// then tile column (one partial each); its pixels [beg[l], beg[l+1]) in the backward.
-struct CensusMulti {
+// Level l's workgroups are [beg[l], beg[l+1]): one tile and one partial each.
+struct CensusMulti : LevelTable {
   const float* img6[8];
   const float* flow[8];
-  float* dcdf[8];           // forward: the plane written (all NULL: value only)
-  const float* plane[8];    // backward: the plane read
-  float* dflow[8];
-  int ld[8];
+  float* dcdf[8];           // the plane written (all NULL: value only)
   float coef[8];
-  int h[8], w[8], tx[8], ty[8];
-  int64_t beg[9];
-  int levels;
 };
 
 __device__ __forceinline__ float census_mean3(float a, float b, float c) {
@@ -97,19 +91,14 @@ __global__ __launch_bounds__(CN_THREADS) void census_fwd_multi(CensusMulti m,
   __shared__ float2 s_gu[HH * HW];      // (g1, u); 0 outside the image (never used: masked)
   __shared__ float2 s_du[HH * HW];      // du/d(flow), read at the tile's own pixels only
   __shared__ float s_w[WT ? HH * HW : 1];   // WT: the weights; 0 outside the image
-  __shared__ float red[CN_THREADS / 64];
 
-  int l = 0;
-  while (l + 1 < m.levels && (int64_t)blockIdx.x >= m.beg[l + 1]) ++l;
+  const int l = level_of(m, blockIdx.x);
   const int h = m.h[l], w = m.w[l];
   const float* img6 = m.img6[l];
   const float* flow = m.flow[l];
-  int t = (int)((int64_t)blockIdx.x - m.beg[l]);
-  const int tcol = t % m.tx[l];
-  t /= m.tx[l];
-  const int trow = t % m.ty[l];
-  const int64_t img = (int64_t)(t / m.ty[l]) * h * w;
-  const int y0 = trow * CN_TY, x0 = tcol * CN_TX;
+  int64_t img;
+  int y0, x0;
+  tile_of<CN_TY, CN_TX>(m, l, blockIdx.x, img, y0, x0);
 
   for (int k = threadIdx.x; k < HH * HW; k += CN_THREADS) {
     const int y = y0 - R + k / HW, x = x0 - R + k % HW;
@@ -164,53 +153,8 @@ __global__ __launch_bounds__(CN_THREADS) void census_fwd_multi(CensusMulti m,
     *reinterpret_cast<float2*>(m.dcdf[l] + 2 * (img + (int64_t)y * w + x)) =
         make_float2(dcdu * du.x, dcdu * du.y);
   }
-  // block reduction in a fixed order: wave shuffles then LDS
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-    for (int k = 0; k < CN_THREADS / 64; ++k) tot += red[k];
-    partials[blockIdx.x] = tot * (m.coef[l] * INV_K);
-  }
-}
-
-__global__ __launch_bounds__(256) void census_bwd_multi(CensusMulti m,
-                                                        const float* __restrict__ dloss,
-                                                        int accumulate) {
-  const int64_t total = m.beg[m.levels];
-  const float dl = dloss ? dloss[0] : 1.f;
-  for (int64_t gp = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; gp < total;
-       gp += (int64_t)gridDim.x * blockDim.x) {
-    int l = 0;
-    while (l + 1 < m.levels && gp >= m.beg[l + 1]) ++l;
-    const int64_t p = gp - m.beg[l];
-    const float2 v = *reinterpret_cast<const float2*>(m.plane[l] + 2 * p);
-    const float c = m.coef[l] * dl;
-    float gx = c * v.x, gy = c * v.y;
-    float* d = m.dflow[l] + (int64_t)m.ld[l] * p;      // channels 2.. of a padded row: untouched
-    if (accumulate) gx += d[0], gy += d[1];
-    d[0] = gx;
-    d[1] = gy;
-  }
-}
-
-// Argument checks shared by both entry points; fills h, w, coef and levels.
-static int census_args(const std::string& f, int n, const int* hs, const int* ws, int levels,
-                       const float* coefs, CensusMulti& m) {
-  if (levels < 1 || levels > 8) return fail(OF_EINVAL, f + ": levels must be 1..8");
-  if (!hs || !ws || !coefs) return fail(OF_EINVAL, f + ": NULL argument");
-  if (n < 1) return fail(OF_EINVAL, f + ": n < 1");
-  m.levels = levels;
-  for (int l = 0; l < levels; ++l) {
-    if (hs[l] < 1 || ws[l] < 1) return fail(OF_EINVAL, f + ": h or w < 1");
-    if ((int64_t)n * hs[l] * ws[l] >= (1LL << 40))
-      return fail(OF_EINVAL, f + ": a level must hold < 2^40 pixels");
-    m.h[l] = hs[l];
-    m.w[l] = ws[l];
-    m.coef[l] = coefs[l];
-  }
-  return OF_OK;
+  const float tot = block_sum_fixed<CN_THREADS>(s);
+  if (threadIdx.x == 0) partials[blockIdx.x] = tot * (m.coef[l] * INV_K);
 }
 
 }  // namespace oflow
@@ -252,28 +196,23 @@ int of_census_fwd_multi_w(const float* const* img6s, const float* const* flows,
   if (convention != OF_WARP_REFERENCE && convention != OF_WARP_IMAGE)
     return fail(OF_EINVAL, fn + ": unknown warp convention");
   CensusMulti m{};
-  const int st = census_args(fn, n, hs, ws, levels, coefs, m);
+  int st = levels_init(fn, n, hs, ws, levels, m);
   if (st) return st;
   if (radius < 1 || radius > CN_RMAX) return fail(OF_EINVAL, fn + ": radius must be 1..3");
-  if (!img6s || !flows) return fail(OF_EINVAL, fn + ": NULL argument");
+  if (!img6s || !flows || !coefs) return fail(OF_EINVAL, fn + ": NULL argument");
   if (!partials) return fail(OF_EINVAL, fn + ": NULL partials");
-  m.beg[0] = 0;
+  if ((st = levels_ptrs8(fn, flows, levels, "flow"))) return st;
+  if (dcdfs && (st = levels_ptrs8(fn, dcdfs, levels, "dcdf"))) return st;
   for (int l = 0; l < levels; ++l) {
     if (!img6s[l]) return fail(OF_EINVAL, fn + ": NULL image level");
-    if (!flows[l] || ((uintptr_t)flows[l] & 7))
-      return fail(OF_EINVAL, fn + ": NULL or not 8-byte aligned flow");
     if (of_census_workspace_floats(n, hs[l], ws[l]) > 0 && (!workspaces || !workspaces[l]))
       return fail(OF_EINVAL, fn + ": NULL workspace");
-    if (dcdfs && (!dcdfs[l] || ((uintptr_t)dcdfs[l] & 7)))
-      return fail(OF_EINVAL, fn + ": NULL or not 8-byte aligned dcdf");
     m.img6[l] = img6s[l];
     m.flow[l] = flows[l];
     m.dcdf[l] = dcdfs ? dcdfs[l] : nullptr;
-    m.tx[l] = (int)cdiv(ws[l], CN_TX);
-    m.ty[l] = (int)cdiv(hs[l], CN_TY);
-    m.beg[l + 1] = m.beg[l] + (int64_t)n * m.ty[l] * m.tx[l];
+    m.coef[l] = coefs[l];
   }
-  if (m.beg[levels] >= INT32_MAX) return fail(OF_EINVAL, fn + ": too many blocks");
+  if ((st = levels_by_tiles(fn, n, m, CN_TY, CN_TX))) return st;
   const dim3 grid((unsigned)m.beg[levels]), block(CN_THREADS);
   const bool im = convention == OF_WARP_IMAGE;
   CensusWeights wt{};
@@ -299,26 +238,8 @@ int of_census_fwd_multi_w(const float* const* img6s, const float* const* flows,
 int of_census_bwd_multi(const float* const* dcdfs, int n, const int* hs, const int* ws,
                         int levels, const float* coefs, const float* dloss,
                         float* const* dflows, const int* lds, int accumulate, void* stream) {
-  static const std::string fn = "of_census_bwd_multi";
-  CensusMulti m{};
-  const int st = census_args(fn, n, hs, ws, levels, coefs, m);
-  if (st) return st;
-  if (!dcdfs || !dflows || !lds) return fail(OF_EINVAL, fn + ": NULL argument");
-  m.beg[0] = 0;
-  for (int l = 0; l < levels; ++l) {
-    if (!dcdfs[l] || ((uintptr_t)dcdfs[l] & 7))
-      return fail(OF_EINVAL, fn + ": NULL or not 8-byte aligned dcdf");
-    if (!dflows[l]) return fail(OF_EINVAL, fn + ": NULL dflow");
-    if (lds[l] < 2) return fail(OF_EINVAL, fn + ": lds[l] must be >= 2");
-    m.plane[l] = dcdfs[l];
-    m.dflow[l] = dflows[l];
-    m.ld[l] = lds[l];
-    m.beg[l + 1] = m.beg[l] + (int64_t)n * hs[l] * ws[l];
-  }
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(m.beg[levels], 256), 8192));
-  hipLaunchKernelGGL(census_bwd_multi, dim3(grid), dim3(256), 0, as_stream(stream), m, dloss,
-                     accumulate);
-  return check_launch("census_bwd_multi");
+  return plane_scale_multi("of_census_bwd_multi", dcdfs, n, hs, ws, levels, coefs, dloss, dflows,
+                           lds, accumulate, stream);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // x2 flow upscale, loss image pyramid, Siamese split, photometric L1 loss.
 //
 // All NHWC fp32.  Each kernel cites the reference call it replaces.
-#include "common.h"
+#include "loss_levels.h"
 #include "warp_tap.h"
 
 namespace oflow {
@@ -1703,30 +1703,19 @@ __global__ __launch_bounds__(PL_THREADS) void photo_l1_fwd_kernel(const float* _
     photo_sample(img6, p, i, j, flow[2 * p], flow[2 * p + 1], h, w, img, diff, t, v);
     s += fabsf(diff[0]) + fabsf(diff[1]) + fabsf(diff[2]);
   }
-  // block reduction: wave shuffles then LDS
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  __shared__ float red[PL_THREADS / 64];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int k = 0; k < PL_THREADS / 64; ++k) t += red[k];
-    partials[blockIdx.x] = t;
-  }
+  const float t = block_sum_fixed<PL_THREADS>(s);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 
-// The photometric loss of every scale in one launch: level l's blocks are [bbeg[l], bbeg[l+1])
+// The photometric loss of every scale in one launch: level l's blocks are [beg[l], beg[l+1])
 // (forward: one partial per block, the partial arrays concatenated in level order) or its
-// pixels [pbeg[l], pbeg[l+1]) (backward: d(flow) of level l at row stride ld[l]).
-struct PhotoMulti {
+// pixels (backward: d(flow) of level l at row stride ld[l]).
+struct PhotoMulti : LevelTable {
   const float* img6[8];
   const float* flow[8];
   float* dflow[8];
   int ld[8];
   float coef[8];
-  int h[8], w[8];
-  int64_t beg[9];
-  int levels;
 };
 // photo_sample's bilinear sum of one channel with every product and sum rounded on its own
 // (no fma): see photo_l1_fwd_multi<CV, true>.
@@ -1747,8 +1736,7 @@ template <int CV, bool WT = false>
 __global__ __launch_bounds__(PL_THREADS) void photo_l1_fwd_multi(int n, PhotoMulti m,
                                                                  float* __restrict__ partials,
                                                                  PhotoWeights wt = {}) {
-  int l = 0;
-  while (l + 1 < m.levels && (int64_t)blockIdx.x >= m.beg[l + 1]) ++l;
+  const int l = level_of(m, blockIdx.x);
   const int h = m.h[l], w = m.w[l];
   const float* img6 = m.img6[l];
   const float* flow = m.flow[l];
@@ -1779,15 +1767,8 @@ __global__ __launch_bounds__(PL_THREADS) void photo_l1_fwd_multi(int n, PhotoMul
       s += fabsf(diff[0]) + fabsf(diff[1]) + fabsf(diff[2]);
     }
   }
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  __shared__ float red[PL_THREADS / 64];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int k = 0; k < PL_THREADS / 64; ++k) t += red[k];
-    partials[blockIdx.x] = t;
-  }
+  const float t = block_sum_fixed<PL_THREADS>(s);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 
 template <int CV, bool WT = false>
@@ -1798,8 +1779,7 @@ __global__ __launch_bounds__(256) void photo_l1_bwd_multi(int n, PhotoMulti m,
   const float dl = dloss ? dloss[0] : 1.f;
   for (int64_t gp = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; gp < total;
        gp += (int64_t)gridDim.x * blockDim.x) {
-    int l = 0;
-    while (l + 1 < m.levels && gp >= m.beg[l + 1]) ++l;
+    const int l = level_of(m, gp);
     const int h = m.h[l], w = m.w[l];
     const float* img6 = m.img6[l];
     const float* flow = m.flow[l];
@@ -1882,10 +1862,6 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(SumArgs a, float* __r
     total += a.coefs[g] * s;
   }
   if (threadIdx.x == 0) out[0] = total;
-}
-
-inline int grid_for(int64_t work, int per_block = 256, int cap = 8192) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(work, per_block), cap));
 }
 
 }  // namespace oflow
@@ -2353,19 +2329,15 @@ int of_photo_l1_fwd_multi_w(const float* const* img6s, const float* const* flows
                             int levels, float* partials, int convention, void* stream) {
   OF_CHECK_ARG(convention == OF_WARP_REFERENCE || convention == OF_WARP_IMAGE,
                "photo l1 fwd multi: unknown warp convention");
-  OF_CHECK_ARG(img6s && flows && hs && ws && partials && levels >= 1 && levels <= 8,
-               "photo l1 fwd multi: args");
   PhotoMulti m{};
-  m.levels = levels;
-  m.beg[0] = 0;
+  if (int st = levels_init("photo l1 fwd multi", n, hs, ws, levels, m)) return st;
+  OF_CHECK_ARG(img6s && flows && partials, "photo l1 fwd multi: args");
   for (int l = 0; l < levels; ++l) {
     OF_CHECK_ARG(img6s[l] && flows[l], "photo l1 fwd multi: NULL level");
     m.img6[l] = img6s[l];
     m.flow[l] = flows[l];
-    m.h[l] = hs[l];
-    m.w[l] = ws[l];
-    m.beg[l + 1] = m.beg[l] + of_photo_l1_partials(n, hs[l], ws[l]);
   }
+  if (int st = levels_by_pixels("photo l1 fwd multi", n, m, PL_PIX_PER_BLOCK)) return st;
   PhotoWeights wt{};
   if (photo_weights(weights, levels, wt)) {
     auto kw = convention == OF_WARP_IMAGE ? photo_l1_fwd_multi<WARP_CV_IMAGE, true>
@@ -2403,11 +2375,10 @@ int of_photo_l1_bwd_multi_w(const float* const* img6s, const float* const* flows
                             float* const* dflows, const int* lds, int convention, void* stream) {
   OF_CHECK_ARG(convention == OF_WARP_REFERENCE || convention == OF_WARP_IMAGE,
                "photo l1 bwd multi: unknown warp convention");
-  OF_CHECK_ARG(img6s && flows && hs && ws && coefs && dflows && lds && levels >= 1 && levels <= 8,
-               "photo l1 bwd multi: args");
   PhotoMulti m{};
-  m.levels = levels;
-  m.beg[0] = 0;
+  if (int st = levels_init("photo l1 bwd multi", n, hs, ws, levels, m)) return st;
+  OF_CHECK_ARG(img6s && flows && coefs && dflows && lds, "photo l1 bwd multi: args");
+  levels_by_pixels("photo l1 bwd multi", n, m);
   for (int l = 0; l < levels; ++l) {
     OF_CHECK_ARG(img6s[l] && flows[l] && dflows[l] && lds[l] >= 2, "photo l1 bwd multi: level");
     m.img6[l] = img6s[l];
@@ -2415,9 +2386,6 @@ int of_photo_l1_bwd_multi_w(const float* const* img6s, const float* const* flows
     m.dflow[l] = dflows[l];
     m.ld[l] = lds[l];
     m.coef[l] = coefs[l];
-    m.h[l] = hs[l];
-    m.w[l] = ws[l];
-    m.beg[l + 1] = m.beg[l] + (int64_t)n * hs[l] * ws[l];
   }
   PhotoWeights wt{};
   if (photo_weights(weights, levels, wt)) {

@@ -16,20 +16,17 @@
 // per destination pixel).  Nothing differentiates through the result.
 #include <algorithm>
 
-#include "common.h"
+#include "loss_levels.h"
 
 namespace oflow {
 
 constexpr int RANGE_SHIFT = 24;                       // accumulator unit 2^-24
 
 // Level l's pixels are [beg[l], beg[l+1]); the accumulators are indexed the same way.
-struct RangeMulti {
+struct RangeMulti : LevelTable {
   const float* flow[8];
   float* range[8];
   float* mask[8];
-  int h[8], w[8];
-  int64_t beg[9];
-  int levels;
 };
 
 __global__ __launch_bounds__(256) void occ_range_zero(unsigned long long* __restrict__ acc,
@@ -50,8 +47,7 @@ __global__ __launch_bounds__(256) void occ_range_splat(int n, int pair_stride, R
   const int64_t total = m.beg[m.levels];
   for (int64_t gp = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; gp < total;
        gp += (int64_t)gridDim.x * blockDim.x) {
-    int l = 0;
-    while (l + 1 < m.levels && gp >= m.beg[l + 1]) ++l;
+    const int l = level_of(m, gp);
     const int h = m.h[l], w = m.w[l];
     const int64_t p = gp - m.beg[l];
     const int j = (int)(p % w);
@@ -84,8 +80,7 @@ __global__ __launch_bounds__(256) void occ_range_finish(
   const int64_t total = m.beg[m.levels];
   for (int64_t gp = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; gp < total;
        gp += (int64_t)gridDim.x * blockDim.x) {
-    int l = 0;
-    while (l + 1 < m.levels && gp >= m.beg[l + 1]) ++l;
+    const int l = level_of(m, gp);
     const int h = m.h[l], w = m.w[l];
     const int64_t p = gp - m.beg[l];
     const float r = (float)ldexp((double)acc[gp], -RANGE_SHIFT);
@@ -130,27 +125,20 @@ int of_occ_range_multi(const float* const* flows, int n, int pair_stride, const 
                        const int* ws, int levels, void* workspace, size_t workspace_bytes,
                        float* const* ranges, float* const* masks, void* stream) {
   static const std::string fn = "of_occ_range_multi";
-  if (levels < 1 || levels > 8) return fail(OF_EINVAL, fn + ": levels must be 1..8");
-  if (!flows || !hs || !ws) return fail(OF_EINVAL, fn + ": NULL argument");
+  RangeMulti m{};
+  int st = levels_init(fn, n, hs, ws, levels, m);
+  if (st) return st;
+  if (!flows) return fail(OF_EINVAL, fn + ": NULL argument");
   if (n < 2 || pair_stride < 1 || (int64_t)n != 2 * (int64_t)pair_stride)
     return fail(OF_EINVAL, fn + ": needs n == 2 * pair_stride, n >= 2");
-  RangeMulti m{};
-  m.levels = levels;
-  m.beg[0] = 0;
+  if ((st = levels_ptrs8(fn, flows, levels, "flow"))) return st;
+  levels_by_pixels(fn, n, m);
   bool any = false;
   for (int l = 0; l < levels; ++l) {
-    if (hs[l] < 1 || ws[l] < 1) return fail(OF_EINVAL, fn + ": h or w < 1");
-    if ((int64_t)n * hs[l] * ws[l] >= (1LL << 40))
-      return fail(OF_EINVAL, fn + ": a level must hold < 2^40 pixels");
-    if (!flows[l] || ((uintptr_t)flows[l] & 7))
-      return fail(OF_EINVAL, fn + ": NULL or not 8-byte aligned flow");
     m.flow[l] = flows[l];
     m.range[l] = ranges ? ranges[l] : nullptr;
     m.mask[l] = masks ? masks[l] : nullptr;
     any = any || m.range[l] || m.mask[l];
-    m.h[l] = hs[l];
-    m.w[l] = ws[l];
-    m.beg[l + 1] = m.beg[l] + (int64_t)n * hs[l] * ws[l];
   }
   if (!workspace || ((uintptr_t)workspace & 7))
     return fail(OF_EINVAL, fn + ": NULL or not 8-byte aligned workspace");
@@ -159,11 +147,11 @@ int of_occ_range_multi(const float* const* flows, int n, int pair_stride, const 
   if (!any) return fail(OF_EINVAL, fn + ": no output: ranges and masks are both NULL");
   unsigned long long* acc = static_cast<unsigned long long*>(workspace);
   const int64_t total = m.beg[levels];
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(total, 256), 8192));
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(occ_range_zero, dim3(grid), dim3(256), 0, st, acc, total);
-  hipLaunchKernelGGL(occ_range_splat, dim3(grid), dim3(256), 0, st, n, pair_stride, m, acc);
-  hipLaunchKernelGGL(occ_range_finish, dim3(grid), dim3(256), 0, st, m, acc);
+  const int grid = grid_for(total);
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(occ_range_zero, dim3(grid), dim3(256), 0, s, acc, total);
+  hipLaunchKernelGGL(occ_range_splat, dim3(grid), dim3(256), 0, s, n, pair_stride, m, acc);
+  hipLaunchKernelGGL(occ_range_finish, dim3(grid), dim3(256), 0, s, m, acc);
   return check_launch("occ_range_multi");
 }
 

@@ -9,19 +9,16 @@
 // float stored per pixel, no atomics, nothing differentiates through the result.
 #include <algorithm>
 
-#include "common.h"
+#include "loss_levels.h"
 #include "warp_tap.h"
 
 namespace oflow {
 
 // Level l's pixels are [beg[l], beg[l+1]).
-struct OccMulti {
+struct OccMulti : LevelTable {
   const float* flow[8];
   float* mask[8];
-  int h[8], w[8];
   float alpha2[8];
-  int64_t beg[9];
-  int levels;
 };
 
 template <int MODE>
@@ -30,8 +27,7 @@ __global__ __launch_bounds__(256) void occ_mask_multi(int n, int pair_stride, fl
   const int64_t total = m.beg[m.levels];
   for (int64_t gp = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; gp < total;
        gp += (int64_t)gridDim.x * blockDim.x) {
-    int l = 0;
-    while (l + 1 < m.levels && gp >= m.beg[l + 1]) ++l;
+    const int l = level_of(m, gp);
     const int h = m.h[l], w = m.w[l];
     const float* flow = m.flow[l];
     const int64_t p = gp - m.beg[l];
@@ -74,9 +70,10 @@ int of_occ_mask_multi(const float* const* flows, int n, int pair_stride, const i
                       const int* ws, int levels, int mode, float alpha1, const float* alpha2s,
                       float* const* masks, void* stream) {
   static const std::string fn = "of_occ_mask_multi";
-  if (levels < 1 || levels > 8) return fail(OF_EINVAL, fn + ": levels must be 1..8");
-  if (!flows || !masks || !hs || !ws) return fail(OF_EINVAL, fn + ": NULL argument");
-  if (n < 1) return fail(OF_EINVAL, fn + ": n < 1");
+  OccMulti m{};
+  int st = levels_init(fn, n, hs, ws, levels, m);
+  if (st) return st;
+  if (!flows || !masks) return fail(OF_EINVAL, fn + ": NULL argument");
   if (mode != OF_OCC_BORDER && mode != OF_OCC_FB) return fail(OF_EINVAL, fn + ": unknown mode");
   if (mode == OF_OCC_FB) {
     if (pair_stride < 1 || (int64_t)n != 2 * (int64_t)pair_stride)
@@ -86,25 +83,16 @@ int of_occ_mask_multi(const float* const* flows, int n, int pair_stride, const i
   } else if (alpha1 < 0.f) {
     return fail(OF_EINVAL, fn + ": alpha1 < 0");
   }
-  OccMulti m{};
-  m.levels = levels;
-  m.beg[0] = 0;
+  if ((st = levels_ptrs8(fn, flows, levels, "flow"))) return st;
   for (int l = 0; l < levels; ++l) {
-    if (hs[l] < 1 || ws[l] < 1) return fail(OF_EINVAL, fn + ": h or w < 1");
-    if ((int64_t)n * hs[l] * ws[l] >= (1LL << 40))
-      return fail(OF_EINVAL, fn + ": a level must hold < 2^40 pixels");
-    if (!flows[l] || ((uintptr_t)flows[l] & 7))
-      return fail(OF_EINVAL, fn + ": NULL or not 8-byte aligned flow");
     if (!masks[l]) return fail(OF_EINVAL, fn + ": NULL mask");
     if (mode == OF_OCC_FB && !(alpha2s[l] >= 0.f)) return fail(OF_EINVAL, fn + ": alpha2 < 0");
     m.flow[l] = flows[l];
     m.mask[l] = masks[l];
-    m.h[l] = hs[l];
-    m.w[l] = ws[l];
     m.alpha2[l] = mode == OF_OCC_FB ? alpha2s[l] : 0.f;
-    m.beg[l + 1] = m.beg[l] + (int64_t)n * hs[l] * ws[l];
   }
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(m.beg[levels], 256), 8192));
+  levels_by_pixels(fn, n, m);
+  const int grid = grid_for(m.beg[levels]);
   hipLaunchKernelGGL(mode == OF_OCC_FB ? occ_mask_multi<OF_OCC_FB> : occ_mask_multi<OF_OCC_BORDER>,
                      dim3(grid), dim3(256), 0, as_stream(stream), n, pair_stride, alpha1, m);
   return check_launch("occ_mask_multi");

@@ -10,7 +10,7 @@
 // its kernels stage an 8 x 32 pixel tile plus halo in LDS (the shape of census_loss.hip).
 #include <algorithm>
 
-#include "common.h"
+#include "loss_levels.h"
 
 namespace oflow {
 
@@ -18,16 +18,14 @@ constexpr int SL_THREADS = 256;
 constexpr int SL_PIX_PER_BLOCK = 1024;
 
 // Level l's blocks are [beg[l], beg[l+1]) in the forward (one partial per block, the partial
-// arrays concatenated in level order), its pixels [beg[l], beg[l+1]) in the backward.
-struct SmoothMulti {
+// arrays concatenated in level order), its pixels [beg[l], beg[l+1]) in the backward; its tiles
+// in both second-order kernels.
+struct SmoothMulti : LevelTable {
   const float* img6[8];     // all NULL when edge_alpha == 0 (no image byte is read)
   const float* flow[8];
   float* dflow[8];
   int ld[8];
   float cv[8], ch[8];
-  int h[8], w[8];
-  int64_t beg[9];
-  int levels;
 };
 
 // Weight of the edge between pixels p and q (image 1 = channels 0..2 of the 6-channel pair).
@@ -60,8 +58,7 @@ template <bool EDGE>
 __global__ __launch_bounds__(SL_THREADS) void flow_smooth_fwd_multi(int n, SmoothMulti m,
                                                                     float alpha, float eps,
                                                                     float* __restrict__ partials) {
-  int l = 0;
-  while (l + 1 < m.levels && (int64_t)blockIdx.x >= m.beg[l + 1]) ++l;
+  const int l = level_of(m, blockIdx.x);
   const int h = m.h[l], w = m.w[l];
   const float* img6 = m.img6[l];
   const float* flow = m.flow[l];
@@ -86,16 +83,8 @@ __global__ __launch_bounds__(SL_THREADS) void flow_smooth_fwd_multi(int n, Smoot
       s += r;
     }
   }
-  // block reduction in a fixed order: wave shuffles then LDS
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  __shared__ float red[SL_THREADS / 64];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int k = 0; k < SL_THREADS / 64; ++k) t += red[k];
-    partials[blockIdx.x] = t;
-  }
+  const float t = block_sum_fixed<SL_THREADS>(s);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 
 template <bool EDGE>
@@ -107,8 +96,7 @@ __global__ __launch_bounds__(256) void flow_smooth_bwd_multi(int n, SmoothMulti 
   const float dl = dloss ? dloss[0] : 1.f;
   for (int64_t gp = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; gp < total;
        gp += (int64_t)gridDim.x * blockDim.x) {
-    int l = 0;
-    while (l + 1 < m.levels && gp >= m.beg[l + 1]) ++l;
+    const int l = level_of(m, gp);
     const int h = m.h[l], w = m.w[l];
     const float* img6 = m.img6[l];
     const float* flow = m.flow[l];
@@ -146,33 +134,22 @@ __global__ __launch_bounds__(256) void flow_smooth_bwd_multi(int n, SmoothMulti 
   }
 }
 
-static int smooth_grid(int64_t work) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(work, 256), 8192));
-}
-
-// Argument checks shared by both entry points; fills the per-level table but not beg[].
+// Argument checks shared by all four entry points; fills the per-level table but not beg[].
 static int smooth_args(const char* fn, const float* const* img6s, const float* const* flows,
                        int n, const int* hs, const int* ws, int levels, float edge_alpha,
                        float eps, const float* coefs_v, const float* coefs_h, SmoothMulti& m) {
   const std::string f(fn);
-  if (levels < 1 || levels > 8) return fail(OF_EINVAL, f + ": levels must be 1..8");
-  if (!flows || !hs || !ws || !coefs_v || !coefs_h) return fail(OF_EINVAL, f + ": NULL argument");
-  if (n < 1) return fail(OF_EINVAL, f + ": n < 1");
+  int st = levels_init(f, n, hs, ws, levels, m);
+  if (st) return st;
+  if (!flows || !coefs_v || !coefs_h) return fail(OF_EINVAL, f + ": NULL argument");
   if (!(eps > 0.f)) return fail(OF_EINVAL, f + ": eps must be > 0");
   if (edge_alpha != 0.f && !img6s)
     return fail(OF_EINVAL, f + ": edge_alpha != 0 needs the image pyramid (img6s is NULL)");
-  m.levels = levels;
+  if ((st = levels_ptrs8(f, flows, levels, "flow"))) return st;
   for (int l = 0; l < levels; ++l) {
-    if (hs[l] < 1 || ws[l] < 1) return fail(OF_EINVAL, f + ": h or w < 1");
-    if ((int64_t)n * hs[l] * ws[l] >= (1LL << 40))
-      return fail(OF_EINVAL, f + ": a level must hold < 2^40 pixels");
-    if (!flows[l] || ((uintptr_t)flows[l] & 7))
-      return fail(OF_EINVAL, f + ": NULL or not 8-byte aligned flow");
     if (edge_alpha != 0.f && !img6s[l]) return fail(OF_EINVAL, f + ": NULL image level");
     m.img6[l] = edge_alpha != 0.f ? img6s[l] : nullptr;
     m.flow[l] = flows[l];
-    m.h[l] = hs[l];
-    m.w[l] = ws[l];
     m.cv[l] = coefs_v[l];
     m.ch[l] = coefs_h[l];
   }
@@ -181,12 +158,6 @@ static int smooth_args(const char* fn, const float* const* img6s, const float* c
 
 // ---------------------------------------------------------------- second order ----
 constexpr int S2_TY = 8, S2_TX = 32, S2_THREADS = S2_TY * S2_TX;
-
-// The tile grid of each level.  Level l's workgroups are [beg[l], beg[l+1]) of SmoothMulti in
-// both kernels: image-major, then tile row, then tile column.
-struct Smooth2Tiles {
-  int tx[8], ty[8];
-};
 
 // Second difference of a triple (outer, centre, outer), products rounded on their own so that
 // forward and backward form the same value.
@@ -230,28 +201,15 @@ struct Smooth2Tile {
   }
 };
 
-// which workgroup of which level: (level, image offset in pixels, tile origin)
-__device__ __forceinline__ int smooth2_tile(const SmoothMulti& m, const Smooth2Tiles& g,
-                                            int64_t& img, int& y0, int& x0) {
-  int l = 0;
-  while (l + 1 < m.levels && (int64_t)blockIdx.x >= m.beg[l + 1]) ++l;
-  int t = (int)((int64_t)blockIdx.x - m.beg[l]);
-  x0 = (t % g.tx[l]) * S2_TX;
-  t /= g.tx[l];
-  y0 = (t % g.ty[l]) * S2_TY;
-  img = (int64_t)(t / g.ty[l]) * m.h[l] * m.w[l];
-  return l;
-}
-
 template <bool EDGE>
 __global__ __launch_bounds__(S2_THREADS) void flow_smooth2_fwd_multi(
-    SmoothMulti m, Smooth2Tiles g, float alpha, float eps, float* __restrict__ partials) {
+    SmoothMulti m, float alpha, float eps, float* __restrict__ partials) {
   using Tile = Smooth2Tile<EDGE, 1>;
   __shared__ Tile s;
-  __shared__ float red[S2_THREADS / 64];
   int64_t img;
   int y0, x0;
-  const int l = smooth2_tile(m, g, img, y0, x0);
+  const int l = level_of(m, blockIdx.x);
+  tile_of<S2_TY, S2_TX>(m, l, blockIdx.x, img, y0, x0);
   const int h = m.h[l], w = m.w[l];
   s.load(m.img6[l], m.flow[l], img, y0, x0, h, w);
   __syncthreads();
@@ -274,15 +232,8 @@ __global__ __launch_bounds__(S2_THREADS) void flow_smooth2_fwd_multi(
            (sqrtf(d.x * d.x + eps) + sqrtf(d.y * d.y + eps));
     }
   }
-  // block reduction in a fixed order: wave shuffles then LDS
-  for (int o = 32; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int k = 0; k < S2_THREADS / 64; ++k) t += red[k];
-    partials[blockIdx.x] = t;
-  }
+  const float t = block_sum_fixed<S2_THREADS>(r);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 
 // t = w2 * rho'(d2) of one triple, both channels
@@ -292,8 +243,7 @@ __device__ __forceinline__ float2 smooth2_t(float2 d, float wt, float eps) {
 
 template <bool EDGE>
 __global__ __launch_bounds__(S2_THREADS) void flow_smooth2_bwd_multi(
-    SmoothMulti m, Smooth2Tiles g, float alpha, float eps, const float* __restrict__ dloss,
-    int accumulate) {
+    SmoothMulti m, float alpha, float eps, const float* __restrict__ dloss, int accumulate) {
   using Tile = Smooth2Tile<EDGE, 2>;
   constexpr int HW = Tile::HW;
   constexpr int NV = (S2_TY + 2) * S2_TX;       // vertical centres: the tile's rows -1 .. TY
@@ -302,7 +252,8 @@ __global__ __launch_bounds__(S2_THREADS) void flow_smooth2_bwd_multi(
   __shared__ float2 tv[NV], th[NH];
   int64_t img;
   int y0, x0;
-  const int l = smooth2_tile(m, g, img, y0, x0);
+  const int l = level_of(m, blockIdx.x);
+  tile_of<S2_TY, S2_TX>(m, l, blockIdx.x, img, y0, x0);
   const int h = m.h[l], w = m.w[l];
   s.load(m.img6[l], m.flow[l], img, y0, x0, h, w);
   __syncthreads();
@@ -349,18 +300,6 @@ __global__ __launch_bounds__(S2_THREADS) void flow_smooth2_bwd_multi(
   d[1] = gy;
 }
 
-// The tile table of both second-order entries (after smooth_args): beg[] and the grid.
-static int smooth2_tiles(const std::string& f, int n, SmoothMulti& m, Smooth2Tiles& g) {
-  m.beg[0] = 0;
-  for (int l = 0; l < m.levels; ++l) {
-    g.tx[l] = (int)cdiv(m.w[l], S2_TX);
-    g.ty[l] = (int)cdiv(m.h[l], S2_TY);
-    m.beg[l + 1] = m.beg[l] + (int64_t)n * g.ty[l] * g.tx[l];
-  }
-  if (m.beg[m.levels] >= INT32_MAX) return fail(OF_EINVAL, f + ": too many blocks");
-  return OF_OK;
-}
-
 }  // namespace oflow
 
 using namespace oflow;
@@ -382,10 +321,7 @@ int of_flow_smooth_fwd_multi(const float* const* img6s, const float* const* flow
                              coefs_h, m);
   if (st) return st;
   if (!partials) return fail(OF_EINVAL, std::string(fn) + ": NULL partials");
-  m.beg[0] = 0;
-  for (int l = 0; l < levels; ++l)
-    m.beg[l + 1] = m.beg[l] + of_flow_smooth_partials(n, hs[l], ws[l]);
-  if (m.beg[levels] >= INT32_MAX) return fail(OF_EINVAL, std::string(fn) + ": too many blocks");
+  if (const int sb = levels_by_pixels(fn, n, m, SL_PIX_PER_BLOCK)) return sb;
   const dim3 grid((unsigned)m.beg[levels]), block(SL_THREADS);
   if (edge_alpha != 0.f)
     hipLaunchKernelGGL(flow_smooth_fwd_multi<true>, grid, block, 0, as_stream(stream), n, m,
@@ -407,15 +343,14 @@ int of_flow_smooth_bwd_multi(const float* const* img6s, const float* const* flow
                              coefs_h, m);
   if (st) return st;
   if (!dflows || !lds) return fail(OF_EINVAL, std::string(fn) + ": NULL argument");
-  m.beg[0] = 0;
   for (int l = 0; l < levels; ++l) {
     if (!dflows[l]) return fail(OF_EINVAL, std::string(fn) + ": NULL dflow");
     if (lds[l] < 2) return fail(OF_EINVAL, std::string(fn) + ": lds[l] must be >= 2");
     m.dflow[l] = dflows[l];
     m.ld[l] = lds[l];
-    m.beg[l + 1] = m.beg[l] + (int64_t)n * hs[l] * ws[l];
   }
-  const dim3 grid(smooth_grid(m.beg[levels])), block(256);
+  levels_by_pixels(fn, n, m);
+  const dim3 grid(grid_for(m.beg[levels])), block(256);
   if (edge_alpha != 0.f)
     hipLaunchKernelGGL(flow_smooth_bwd_multi<true>, grid, block, 0, as_stream(stream), n, m,
                        edge_alpha, eps, dloss, accumulate);
@@ -436,17 +371,16 @@ int of_flow_smooth2_fwd_multi(const float* const* img6s, const float* const* flo
                               float* partials, void* stream) {
   static const char* fn = "of_flow_smooth2_fwd_multi";
   SmoothMulti m{};
-  Smooth2Tiles g{};
   int st = smooth_args(fn, img6s, flows, n, hs, ws, levels, edge_alpha, eps, coefs_v, coefs_h, m);
   if (st) return st;
   if (!partials) return fail(OF_EINVAL, std::string(fn) + ": NULL partials");
-  if ((st = smooth2_tiles(fn, n, m, g))) return st;
+  if ((st = levels_by_tiles(fn, n, m, S2_TY, S2_TX))) return st;
   const dim3 grid((unsigned)m.beg[levels]), block(S2_THREADS);
   if (edge_alpha != 0.f)
-    hipLaunchKernelGGL(flow_smooth2_fwd_multi<true>, grid, block, 0, as_stream(stream), m, g,
+    hipLaunchKernelGGL(flow_smooth2_fwd_multi<true>, grid, block, 0, as_stream(stream), m,
                        edge_alpha, eps, partials);
   else
-    hipLaunchKernelGGL(flow_smooth2_fwd_multi<false>, grid, block, 0, as_stream(stream), m, g,
+    hipLaunchKernelGGL(flow_smooth2_fwd_multi<false>, grid, block, 0, as_stream(stream), m,
                        edge_alpha, eps, partials);
   return check_launch("flow_smooth2_fwd_multi");
 }
@@ -458,7 +392,6 @@ int of_flow_smooth2_bwd_multi(const float* const* img6s, const float* const* flo
                               int accumulate, void* stream) {
   static const char* fn = "of_flow_smooth2_bwd_multi";
   SmoothMulti m{};
-  Smooth2Tiles g{};
   int st = smooth_args(fn, img6s, flows, n, hs, ws, levels, edge_alpha, eps, coefs_v, coefs_h, m);
   if (st) return st;
   if (!dflows || !lds) return fail(OF_EINVAL, std::string(fn) + ": NULL argument");
@@ -468,13 +401,13 @@ int of_flow_smooth2_bwd_multi(const float* const* img6s, const float* const* flo
     m.dflow[l] = dflows[l];
     m.ld[l] = lds[l];
   }
-  if ((st = smooth2_tiles(fn, n, m, g))) return st;
+  if ((st = levels_by_tiles(fn, n, m, S2_TY, S2_TX))) return st;
   const dim3 grid((unsigned)m.beg[levels]), block(S2_THREADS);
   if (edge_alpha != 0.f)
-    hipLaunchKernelGGL(flow_smooth2_bwd_multi<true>, grid, block, 0, as_stream(stream), m, g,
+    hipLaunchKernelGGL(flow_smooth2_bwd_multi<true>, grid, block, 0, as_stream(stream), m,
                        edge_alpha, eps, dloss, accumulate);
   else
-    hipLaunchKernelGGL(flow_smooth2_bwd_multi<false>, grid, block, 0, as_stream(stream), m, g,
+    hipLaunchKernelGGL(flow_smooth2_bwd_multi<false>, grid, block, 0, as_stream(stream), m,
                        edge_alpha, eps, dloss, accumulate);
   return check_launch("flow_smooth2_bwd_multi");
 }

@@ -15,7 +15,7 @@
 // is not interior.  Phase 3: each tile pixel box-sums the coefficients of its up to nine
 // windows and writes d SSIM_l / d(flow) as a dense plane, zeros included.  One partial per
 // workgroup (wave shuffles, then LDS), no atomics: run-to-run bitwise equal.  The plane is
-// scaled into d(flow) by census_bwd_multi (of_ssim_bwd_multi is of_census_bwd_multi).
+// scaled into d(flow) by plane_scale_multi (loss_levels.h).
 //
 // Numerics: LDS holds x and y relative to a per-tile, per-channel reference (the stored values
 // of the tile's first pixel), so that the window means and the affine gradient form work on
@@ -24,7 +24,7 @@
 // the same number as the definition's, without the cancellation near S = 1.
 #include <algorithm>
 
-#include "common.h"
+#include "loss_levels.h"
 #include "warp_tap.h"
 
 namespace oflow {
@@ -36,17 +36,13 @@ constexpr int SS_HALO = SS_SW * SS_SH - SS_THREADS;      // 176 halo pixels
 constexpr float SS_C1 = 0.01f * 0.01f, SS_C2 = 0.03f * 0.03f;
 static_assert(SS_HALO <= SS_THREADS, "one halo pixel per thread");
 
-// Level l's workgroups are [beg[l], beg[l+1]): image-major, then tile row, then tile column
-// (one partial each).
-struct SsimMulti {
+// Level l's workgroups are [beg[l], beg[l+1]): one tile and one partial each.
+struct SsimMulti : LevelTable {
   const float* img6[8];
   const float* flow[8];
   const float* wt[8];       // (n,h,w) centre weights; NULL: 1
   float* dsdf[8];           // the plane written (all NULL: value only)
   float coef[8];
-  int h[8], w[8], tx[8], ty[8];
-  int64_t beg[9];
-  int levels;
 };
 
 __device__ __forceinline__ float ssim_mean(int c) {
@@ -88,8 +84,10 @@ __global__ __launch_bounds__(SS_THREADS) void ssim_fwd_multi(SsimMulti m,
   __shared__ float s_y[3][SS_SH * SS_SW];     // y - ry
   __shared__ float s_k[9][SS_CH * SS_CW];     // per centre and channel c: a, b, c at 3c + 0..2
   __shared__ float s_ref[6];                  // rx, ry
-  __shared__ float red[SS_THREADS / 64];
 
+  // The level search and the tile decode are spelled out here, not taken from loss_levels.h:
+  // through level_of() or tile_of() the compiler fuses and pairs the unpinned products of
+  // ssim_sample and of phase 3 differently, and the term and its planes move by an ulp.
   int l = 0;
   while (l + 1 < m.levels && (int64_t)blockIdx.x >= m.beg[l + 1]) ++l;
   const int h = m.h[l], w = m.w[l];
@@ -233,15 +231,8 @@ __global__ __launch_bounds__(SS_THREADS) void ssim_fwd_multi(SsimMulti m,
           make_float2(gx, gy);
     }
   }
-  // block reduction in a fixed order: wave shuffles then LDS
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) {
-    float tot = 0.f;
-    for (int k = 0; k < SS_THREADS / 64; ++k) tot += red[k];
-    partials[blockIdx.x] = tot * m.coef[l];
-  }
+  const float tot = block_sum_fixed<SS_THREADS>(s);
+  if (tid == 0) partials[blockIdx.x] = tot * m.coef[l];
 }
 
 }  // namespace oflow
@@ -262,36 +253,24 @@ int of_ssim_fwd_multi(const float* const* img6s, const float* const* flows,
   static const std::string fn = "of_ssim_fwd_multi";
   if (convention != OF_WARP_REFERENCE && convention != OF_WARP_IMAGE)
     return fail(OF_EINVAL, fn + ": unknown warp convention");
-  if (levels < 1 || levels > 8) return fail(OF_EINVAL, fn + ": levels must be 1..8");
-  if (!img6s || !flows || !hs || !ws || !coefs) return fail(OF_EINVAL, fn + ": NULL argument");
-  if (!partials) return fail(OF_EINVAL, fn + ": NULL partials");
-  if (n < 1) return fail(OF_EINVAL, fn + ": n < 1");
   SsimMulti m{};
-  m.levels = levels;
-  m.beg[0] = 0;
+  int st = levels_init(fn, n, hs, ws, levels, m);
+  if (st) return st;
+  if (!img6s || !flows || !coefs) return fail(OF_EINVAL, fn + ": NULL argument");
+  if (!partials) return fail(OF_EINVAL, fn + ": NULL partials");
+  if ((st = levels_ptrs8(fn, flows, levels, "flow"))) return st;
+  if (dsdfs && (st = levels_ptrs8(fn, dsdfs, levels, "dsdf"))) return st;
   bool weighted = false;          // a NULL array or only NULL entries: the unweighted kernel
   for (int l = 0; l < levels; ++l) {
-    if (hs[l] < 1 || ws[l] < 1) return fail(OF_EINVAL, fn + ": h or w < 1");
-    if ((int64_t)n * hs[l] * ws[l] >= (1LL << 40))
-      return fail(OF_EINVAL, fn + ": a level must hold < 2^40 pixels");
     if (!img6s[l]) return fail(OF_EINVAL, fn + ": NULL image level");
-    if (!flows[l] || ((uintptr_t)flows[l] & 7))
-      return fail(OF_EINVAL, fn + ": NULL or not 8-byte aligned flow");
-    if (dsdfs && (!dsdfs[l] || ((uintptr_t)dsdfs[l] & 7)))
-      return fail(OF_EINVAL, fn + ": NULL or not 8-byte aligned dsdf");
     m.img6[l] = img6s[l];
     m.flow[l] = flows[l];
     m.wt[l] = weights ? weights[l] : nullptr;
     weighted = weighted || m.wt[l];
     m.dsdf[l] = dsdfs ? dsdfs[l] : nullptr;
     m.coef[l] = coefs[l];
-    m.h[l] = hs[l];
-    m.w[l] = ws[l];
-    m.tx[l] = (int)cdiv(ws[l], SS_TX);
-    m.ty[l] = (int)cdiv(hs[l], SS_TY);
-    m.beg[l + 1] = m.beg[l] + (int64_t)n * m.ty[l] * m.tx[l];
   }
-  if (m.beg[levels] >= INT32_MAX) return fail(OF_EINVAL, fn + ": too many blocks");
+  if ((st = levels_by_tiles(fn, n, m, SS_TY, SS_TX))) return st;
   const dim3 grid((unsigned)m.beg[levels]), block(SS_THREADS);
   const bool im = convention == OF_WARP_IMAGE;
   auto k = weighted ? (im ? ssim_fwd_multi<WARP_CV_IMAGE, true> : ssim_fwd_multi<WARP_CV_REFERENCE, true>)
@@ -300,12 +279,11 @@ int of_ssim_fwd_multi(const float* const* img6s, const float* const* flows,
   return check_launch("ssim_fwd_multi");
 }
 
-// Scaling a plane into d(flow) is what census_bwd_multi does: the same kernel.
 int of_ssim_bwd_multi(const float* const* dsdfs, int n, const int* hs, const int* ws, int levels,
                       const float* coefs, const float* dloss, float* const* dflows,
                       const int* lds, int accumulate, void* stream) {
-  return of_census_bwd_multi(dsdfs, n, hs, ws, levels, coefs, dloss, dflows, lds, accumulate,
-                             stream);
+  return plane_scale_multi("of_ssim_bwd_multi", dsdfs, n, hs, ws, levels, coefs, dloss, dflows,
+                           lds, accumulate, stream);
 }
 
 }  // extern "C"

@@ -23,8 +23,8 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
 #include "flow_sample.h"
+#include "loss_levels.h"
 
 using namespace oflow;
 
@@ -37,14 +37,12 @@ constexpr int kCntThreads = 256;
 constexpr int kCntPxPerWg = 4096;
 constexpr int kCntMaxWgs = 256;
 
-struct SupMulti {
+// h, w: each level's flow grid; beg[l]: the first workgroup of level l.
+struct SupMulti : LevelTable {
   const float* flow[8];
   float* plane[8];        // may be NULL: no gradient wanted
-  int fh[8], fw[8];
   float coef[8];
   int split[8];           // waves per cell: 1 or kSupWaves
-  int64_t beg[9];         // first workgroup of each level
-  int levels;
 };
 
 int count_partials_per_image(int max_gh, int max_gw) {
@@ -149,9 +147,8 @@ __global__ __launch_bounds__(kSupThreads) void sup_fwd_multi(
   __shared__ float2 s_tile[kSupWaves][9];
   __shared__ double s_red[kSupWaves][3];
   const int tid = threadIdx.x, wave = tid / kWave, lane = tid & (kWave - 1);
-  int l = 0;
-  while (l + 1 < m.levels && (int64_t)blockIdx.x >= m.beg[l + 1]) ++l;
-  const int fh = m.fh[l], fw = m.fw[l], S = m.split[l], cpw = kSupWaves / S;
+  const int l = level_of(m, blockIdx.x);
+  const int fh = m.h[l], fw = m.w[l], S = m.split[l], cpw = kSupWaves / S;
   const int ncell = fh * fw;
   const int bpi = (ncell + cpw - 1) / cpw;
   const int r = (int)((int64_t)blockIdx.x - m.beg[l]);
@@ -281,10 +278,12 @@ int of_supervised_fwd_multi(const float* const* flows, int n, int n_gt, const in
                             int64_t workspace_bytes, float* const* dsdfs, float* partials,
                             void* stream) {
   static const std::string fn = "of_supervised_fwd_multi";
-  if (levels < 1 || levels > 8) return fail(OF_EINVAL, fn + ": levels must be 1..8");
-  if (!flows || !fhs || !fws || !coefs || !dev_gt_raw || !workspace || !partials)
-    return fail(OF_EINVAL, fn + ": NULL argument");
+  SupMulti m{};
   if (n < 1 || n > 65535) return fail(OF_EINVAL, fn + ": n outside 1..65535");
+  int st = levels_init(fn, n, fhs, fws, levels, m, "flow grid size < 1");
+  if (st) return st;
+  if (!flows || !coefs || !dev_gt_raw || !workspace || !partials)
+    return fail(OF_EINVAL, fn + ": NULL argument");
   if (n_gt < 1 || n_gt > n) return fail(OF_EINVAL, fn + ": n_gt outside 1..n");
   if (!(q > 0.f && q <= 2.f)) return fail(OF_EINVAL, fn + ": q must be in (0, 2]");
   if (!(eps > 0.f) || !std::isfinite(eps)) return fail(OF_EINVAL, fn + ": eps must be > 0");
@@ -294,21 +293,14 @@ int of_supervised_fwd_multi(const float* const* flows, int n, int n_gt, const in
     return fail(OF_EINVAL, fn + ": workspace not 16-byte aligned or smaller than "
                                 "of_supervised_workspace_bytes(...)");
   if ((uintptr_t)partials & 3) return fail(OF_EINVAL, fn + ": partials must be 4-byte aligned");
-  SupMulti m{};
-  m.levels = levels;
-  m.beg[0] = 0;
+  if ((st = levels_ptrs8(fn, flows, levels, "flow"))) return st;
+  if (dsdfs && (st = levels_ptrs8(fn, dsdfs, levels, "plane"))) return st;
+  m.beg[0] = 0;       // a level's workgroups depend on its split: no levels_by_*()
   for (int l = 0; l < levels; ++l) {
-    if (fhs[l] < 1 || fws[l] < 1) return fail(OF_EINVAL, fn + ": flow grid size < 1");
     if ((int64_t)fhs[l] * fws[l] >= INT32_MAX / 4)
       return fail(OF_EINVAL, fn + ": a level must hold < 2^29 cells per image");
-    if (!flows[l] || ((uintptr_t)flows[l] & 7))
-      return fail(OF_EINVAL, fn + ": NULL or not 8-byte aligned flow");
-    if (dsdfs && (!dsdfs[l] || ((uintptr_t)dsdfs[l] & 7)))
-      return fail(OF_EINVAL, fn + ": NULL or not 8-byte aligned plane");
     m.flow[l] = flows[l];
     m.plane[l] = dsdfs ? dsdfs[l] : nullptr;
-    m.fh[l] = fhs[l];
-    m.fw[l] = fws[l];
     m.coef[l] = coefs[l];
     m.split[l] = level_split(fhs[l], fws[l], max_gh, max_gw);
     m.beg[l + 1] = m.beg[l] + level_blocks(n, fhs[l], fws[l], m.split[l]);

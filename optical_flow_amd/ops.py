@@ -8,7 +8,7 @@ from __future__ import annotations
 import contextlib
 import os
 import ctypes as C
-from typing import NamedTuple, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -2111,16 +2111,53 @@ def halves(x):
 
 
 # ================================================================ photometric loss =====
-# The training loss: photometric, census, SSIM and smoothness terms over one image pyramid, in
-# one autograd Function (_Loss, below).  Each term has a forward and a backward helper of the
-# same shape; ``lv`` is the list of (level, output, row stride) that _grad_targets builds.
+# The training loss: photometric, census, SSIM, supervised, self-supervision and smoothness
+# terms over one image pyramid, in one autograd Function (_Loss, below) that walks a table of
+# terms (_TERMS).  A term's forward returns (sum groups, tensors to save, its own state); a sum
+# group is (partials, first float, count, coefficient).  Its backward gets that state and those
+# tensors back, with the saved pyramid and flows, and ``lv``, the list of (level, output, row
+# stride) that _grad_targets builds.
 def _arr(ctype, vals):
     return (ctype * len(vals))(*vals)
+
+
+def _ptrs(ts):
+    return _arr(C.c_void_p, [t.data_ptr() for t in ts])
 
 
 def _opt_ptrs(ts):
     """A pointer array over tensors; None entries become NULL."""
     return _arr(C.c_void_p, [t.data_ptr() if t is not None else None for t in ts])
+
+
+def _dims(ts):
+    """n, the heights and the widths of per-level (n, h, w, c) tensors."""
+    return ts[0].shape[0], [t.shape[1] for t in ts], [t.shape[2] for t in ts]
+
+
+def _levels(ts):
+    """The per-level arguments every multi entry takes: n, hs, ws, the level count."""
+    n, hs, ws = _dims(ts)
+    return n, _arr(C.c_int, hs), _arr(C.c_int, ws), len(ts)
+
+
+def _at(xs, lv):
+    """The entries of a per-level list for the levels in ``lv``."""
+    return [xs[k] for k, _, _ in lv]
+
+
+def _outs(lv):
+    """The d(flow) outputs of a backward entry: pointers and row strides."""
+    return _ptrs([o for _, o, _ in lv]), _arr(C.c_int, [ld for _, _, ld in lv])
+
+
+def _planes(fl, want_grad):
+    """(planes, their pointer array) for a forward that writes d(term)/d(flow) densely; (None,
+    NULL) without want_grad."""
+    if not want_grad:
+        return None, None
+    planes = [torch.empty_like(f) for f in fl]
+    return planes, _ptrs(planes)
 
 
 def _pyramid6(b, flows):
@@ -2136,53 +2173,51 @@ def _pyramid6(b, flows):
         assert f.shape[1] == h and f.shape[2] == w, \
             "flow %d has shape %s, expected (B,%d,%d,2)" % (k, tuple(f.shape), h, w)
         pyr.append(torch.empty((n, h, w, 6), device=b.device))
-    call("of_pyramid6", _ptr(b), n, H, W, len(pyr), _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
-         _stream())
+    call("of_pyramid6", _ptr(b), n, H, W, len(pyr), _ptrs(pyr), _stream())
     return pyr
 
 
-# Which C entry serves a data term: the plain name in the reference convention without pixel
-# weights (the call it always was), its ``_cv`` form in the image convention (_call_cv), its
-# ``_w`` form, which takes both the weights and the convention, when weights are given.
-def _photo_fwd(pyr, fl, wts, wc):
+def _call_data(name, wc, wts, imgs, fls, *rest):
+    """Which C entry serves a data term: the plain name in the reference convention without
+    pixel weights (the call it always was), its ``_cv`` form in the image convention
+    (_call_cv), its ``_w`` form, which takes the weights after the flows and the convention
+    before the stream, when weights are given."""
+    if wts is not None:
+        return call(name + "_w", imgs, fls, _opt_ptrs(wts), *rest, wc, _stream())
+    return _call_cv(name, wc, imgs, fls, *rest, _stream())
+
+
+def _planes_bwd(entry, planes, lv, coefs, dloss, accumulate):
+    """``entry`` (of_census_bwd_multi, of_ssim_bwd_multi: the pixelwise plane scaling) for the
+    levels in ``lv``: coefs[l] * dloss * planes[l] written to or added into d(flow)."""
+    lp = _at(planes, lv)
+    call(entry, _ptrs(lp), *_levels(lp), _arr(C.c_float, _at(coefs, lv)), _ptr(dloss),
+         *_outs(lv), accumulate, _stream())
+
+
+def _photo_fwd(cfg, pyr, fl, want_grad):
     """of_photo_l1_fwd_multi over every level (LossLayer.__call__, loss.py:5-32: the warp, the
-    difference, |.| and the reduction fused per scale): (partials, per-level counts).  Level
-    l's slice sums to its unscaled sum of |img1 - warp(img2)|; the caller's sum applies the
-    coefficients.  ``wts``: per-level pixel weights, None for the unweighted call."""
-    ns = len(fl)
-    n = fl[0].shape[0]
-    hs = [p.shape[1] for p in pyr]
-    ws_ = [p.shape[2] for p in pyr]
-    nparts = [_lib.lib().of_photo_l1_partials(n, h, w) for h, w in zip(hs, ws_)]
+    difference, |.| and the reduction fused per scale).  Level l's slice of the partials sums to
+    its unscaled sum of |img1 - warp(img2)|: one sum group per level, which applies the
+    coefficient.  The backward reads the pixel weights again."""
+    n, hs, ws = _dims(pyr)
+    coefs = [cfg.pw / (len(fl) * n * h * w * 3) for h, w in zip(hs, ws)]
+    nparts = [_lib.lib().of_photo_l1_partials(n, h, w) for h, w in zip(hs, ws)]
     parts = torch.empty(sum(nparts), device=fl[0].device)
-    imgs = _arr(C.c_void_p, [p.data_ptr() for p in pyr])
-    fls = _arr(C.c_void_p, [f.data_ptr() for f in fl])
-    if wts is not None:
-        call("of_photo_l1_fwd_multi_w", imgs, fls, _opt_ptrs(wts), n, _arr(C.c_int, hs),
-             _arr(C.c_int, ws_), ns, _ptr(parts), wc, _stream())
-    else:
-        _call_cv("of_photo_l1_fwd_multi", wc, imgs, fls, n, _arr(C.c_int, hs),
-                 _arr(C.c_int, ws_), ns, _ptr(parts), _stream())
-    return parts, nparts
+    _call_data("of_photo_l1_fwd_multi", cfg.wc, cfg.wts, _ptrs(pyr), _ptrs(fl), *_levels(pyr),
+               _ptr(parts))
+    firsts = [sum(nparts[:k]) for k in range(len(fl))]
+    return list(zip([parts] * len(fl), firsts, nparts, coefs)), [], (coefs, cfg.wts)
 
 
-def _photo_bwd(pyr, flows, wts, lv, coefs, dloss, wc):
+def _photo_bwd(cfg, state, own, pyr, flows, lv, dloss, accumulate):
     """of_photo_l1_bwd_multi for the levels in ``lv``: writes (never adds) each level's
-    d(flow); the images are constants."""
-    m = len(lv)
-    n = pyr[0].shape[0]
-    imgs = _arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv])
-    fls = _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv])
-    tail = (_arr(C.c_int, [pyr[k].shape[1] for k, _, _ in lv]),
-            _arr(C.c_int, [pyr[k].shape[2] for k, _, _ in lv]), m,
-            _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
-            _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
-            _arr(C.c_int, [ld for _, _, ld in lv]))
-    if wts is not None:
-        call("of_photo_l1_bwd_multi_w", imgs, fls, _opt_ptrs([wts[k] for k, _, _ in lv]), n,
-             *tail, wc, _stream())
-    else:
-        _call_cv("of_photo_l1_bwd_multi", wc, imgs, fls, n, *tail, _stream())
+    d(flow), so the photometric term is the first of the table; the images are constants."""
+    coefs, wts = state
+    lp = _at(pyr, lv)
+    _call_data("of_photo_l1_bwd_multi", cfg.wc, _at(wts, lv) if wts is not None else None,
+               _ptrs(lp), _ptrs(_at(flows, lv)), *_levels(lp), _arr(C.c_float, _at(coefs, lv)),
+               _ptr(dloss), *_outs(lv))
 
 
 # ============================================================== flow smoothness =====
@@ -2206,42 +2241,32 @@ def _smooth_coefs(n, hs, ws, scale, order=1):
     return cv, ch
 
 
-def _smooth_fwd(pyr, fl, edge_alpha, eps, cv, ch, order=1):
+def _smooth_fwd(cfg, pyr, fl, want_grad):
     """of_flow_smooth_fwd_multi over every level (include/oflow.h): the mean Charbonnier
     penalty of the vertical plus that of the horizontal first differences of the flow, each
-    weighted by exp(-edge_alpha * mean|d image1|) across the same pair.  Returns the partials
-    (they sum to the weighted term, the coefficients are applied in the kernel).  The images
-    are only read when ``edge_alpha`` is not 0.  ``order`` 2: of_flow_smooth2_fwd_multi, the
-    second differences, weighted across each triple's two outer pixels."""
-    ns = len(fl)
-    n = fl[0].shape[0]
-    hs = [f.shape[1] for f in fl]
-    ws_ = [f.shape[2] for f in fl]
-    entry = _SMOOTH_ENTRIES[order]
+    weighted by exp(-edge_alpha * mean|d image1|) across the same pair.  The partials sum to
+    the weighted term (the coefficients are applied in the kernel).  The images are only read
+    when ``edge_alpha`` is not 0.  Order 2: of_flow_smooth2_fwd_multi, the second differences,
+    weighted across each triple's two outer pixels."""
+    n, hs, ws = _dims(fl)
+    cv, ch = _smooth_coefs(n, hs, ws, cfg.sw, cfg.order)
+    entry = _SMOOTH_ENTRIES[cfg.order]
     count = getattr(_lib.lib(), entry + "_partials")
-    nparts = sum(count(n, h, w) for h, w in zip(hs, ws_))
-    parts = torch.empty(nparts, device=fl[0].device)
-    imgs = _arr(C.c_void_p, [p.data_ptr() for p in pyr]) if edge_alpha != 0 else None
-    call(entry + "_fwd_multi", imgs, _arr(C.c_void_p, [f.data_ptr() for f in fl]), n,
-         _arr(C.c_int, hs), _arr(C.c_int, ws_), ns, edge_alpha, eps, _arr(C.c_float, cv),
-         _arr(C.c_float, ch), _ptr(parts), _stream())
-    return parts
+    parts = torch.empty(sum(count(n, h, w) for h, w in zip(hs, ws)), device=fl[0].device)
+    call(entry + "_fwd_multi", _ptrs(pyr) if cfg.edge_alpha != 0 else None, _ptrs(fl),
+         *_levels(fl), cfg.edge_alpha, cfg.eps, _arr(C.c_float, cv), _arr(C.c_float, ch),
+         _ptr(parts), _stream())
+    return [(parts, 0, parts.numel(), 1.0)], [], (cv, ch)
 
 
-def _smooth_bwd(pyr, flows, lv, edge_alpha, eps, cv, ch, dloss, accumulate, order=1):
-    """of_flow_smooth_bwd_multi (``order`` 2: of_flow_smooth2_bwd_multi) for the levels in
-    ``lv``."""
-    m = len(lv)
-    n = flows[0].shape[0]
-    imgs = (_arr(C.c_void_p, [pyr[k].data_ptr() for k, _, _ in lv]) if edge_alpha != 0
-            else None)
-    call(_SMOOTH_ENTRIES[order] + "_bwd_multi", imgs,
-         _arr(C.c_void_p, [flows[k].data_ptr() for k, _, _ in lv]), n,
-         _arr(C.c_int, [flows[k].shape[1] for k, _, _ in lv]),
-         _arr(C.c_int, [flows[k].shape[2] for k, _, _ in lv]), m, edge_alpha, eps,
-         _arr(C.c_float, [cv[k] for k, _, _ in lv]), _arr(C.c_float, [ch[k] for k, _, _ in lv]),
-         _ptr(dloss), _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
-         _arr(C.c_int, [ld for _, _, ld in lv]), accumulate, _stream())
+def _smooth_bwd(cfg, state, own, pyr, flows, lv, dloss, accumulate):
+    """of_flow_smooth_bwd_multi (order 2: of_flow_smooth2_bwd_multi) for the levels in ``lv``."""
+    cv, ch = state
+    lf = _at(flows, lv)
+    call(_SMOOTH_ENTRIES[cfg.order] + "_bwd_multi",
+         _ptrs(_at(pyr, lv)) if cfg.edge_alpha != 0 else None, _ptrs(lf), *_levels(lf),
+         cfg.edge_alpha, cfg.eps, _arr(C.c_float, _at(cv, lv)), _arr(C.c_float, _at(ch, lv)),
+         _ptr(dloss), *_outs(lv), accumulate, _stream())
 
 
 # ================================================================== census term =====
@@ -2252,47 +2277,27 @@ def _census_coefs(n, hs, ws, scale):
     return [scale / (ns * n * h * w) for h, w in zip(hs, ws)]
 
 
-def _census_fwd(pyr, fl, radius, coefs, want_grad, wc=0, wts=None):
-    """of_census_fwd_multi over every level (the soft ternary census term, include/oflow.h):
-    (partials, planes).  The partials sum to the weighted term (the coefficients are applied
-    in the kernel); planes[l] is the unscaled d C_l / d flow (the window loop forms both) that
-    of_census_bwd_multi scales into d(flow), or None without want_grad.
-    ``wts``: per-level pixel weights (of_census_fwd_multi_w), None for the unweighted call."""
+def _census_fwd(cfg, pyr, fl, want_grad):
+    """of_census_fwd_multi over every level (the soft ternary census term, include/oflow.h).
+    The partials sum to the weighted term (the coefficients are applied in the kernel);
+    planes[l] is the unscaled d C_l / d flow (the window loop forms both) that
+    of_census_bwd_multi scales into d(flow)."""
     lib = _lib.lib()
-    ns = len(fl)
-    n = fl[0].shape[0]
-    hs = [f.shape[1] for f in fl]
-    ws_ = [f.shape[2] for f in fl]
-    parts = torch.empty(sum(lib.of_census_partials(n, h, w) for h, w in zip(hs, ws_)),
+    n, hs, ws = _dims(fl)
+    coefs = _census_coefs(n, hs, ws, cfg.cw)
+    parts = torch.empty(sum(lib.of_census_partials(n, h, w) for h, w in zip(hs, ws)),
                         device=fl[0].device)
-    planes = [torch.empty_like(f) for f in fl] if want_grad else None
-    wsf = [lib.of_census_workspace_floats(n, h, w) for h, w in zip(hs, ws_)]
+    planes, plp = _planes(fl, want_grad)
+    wsf = [lib.of_census_workspace_floats(n, h, w) for h, w in zip(hs, ws)]
     wss = [torch.empty(k, device=fl[0].device) if k > 0 else None for k in wsf]
-    wsp = _opt_ptrs(wss) if any(wsf) else None
-    plp = _arr(C.c_void_p, [p.data_ptr() for p in planes]) if planes is not None else None
-    if wts is not None:
-        call("of_census_fwd_multi_w", _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
-             _arr(C.c_void_p, [f.data_ptr() for f in fl]), _opt_ptrs(wts), n,
-             _arr(C.c_int, hs), _arr(C.c_int, ws_), ns, radius, _arr(C.c_float, coefs), wsp, plp,
-             _ptr(parts), wc, _stream())
-        return parts, planes
-    _call_cv("of_census_fwd_multi", wc, _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
-             _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, _arr(C.c_int, hs),
-             _arr(C.c_int, ws_), ns, radius, _arr(C.c_float, coefs), wsp, plp,
-             _ptr(parts), _stream())
-    return parts, planes
+    _call_data("of_census_fwd_multi", cfg.wc, cfg.wts, _ptrs(pyr), _ptrs(fl), *_levels(fl),
+               cfg.radius, _arr(C.c_float, coefs), _opt_ptrs(wss) if any(wsf) else None, plp,
+               _ptr(parts))
+    return [(parts, 0, parts.numel(), 1.0)], planes or [], coefs
 
 
-def _census_bwd(planes, lv, coefs, dloss, accumulate):
-    """of_census_bwd_multi for the levels in ``lv``."""
-    m = len(lv)
-    n = planes[0].shape[0]
-    call("of_census_bwd_multi", _arr(C.c_void_p, [planes[k].data_ptr() for k, _, _ in lv]), n,
-         _arr(C.c_int, [planes[k].shape[1] for k, _, _ in lv]),
-         _arr(C.c_int, [planes[k].shape[2] for k, _, _ in lv]), m,
-         _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
-         _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
-         _arr(C.c_int, [ld for _, _, ld in lv]), accumulate, _stream())
+def _census_bwd(cfg, coefs, planes, pyr, flows, lv, dloss, accumulate):
+    _planes_bwd("of_census_bwd_multi", planes, lv, coefs, dloss, accumulate)
 
 
 # ==================================================================== SSIM term =====
@@ -2304,38 +2309,31 @@ def _ssim_coefs(n, hs, ws, scale):
             for h, w in zip(hs, ws)]
 
 
-def _ssim_fwd(pyr, fl, coefs, want_grad, wc=0, wts=None):
-    """of_ssim_fwd_multi over every level (the SSIM data term, include/oflow.h): (partials,
-    planes).  The partials sum to the weighted term (the coefficients are applied in the
-    kernel); planes[l] is the unscaled d SSIM_l / d flow, every element written, that
-    of_ssim_bwd_multi scales into d(flow), or None without want_grad.  ``wts``: per-level
-    pixel weights of the window centres, None for weight 1."""
-    lib = _lib.lib()
-    ns = len(fl)
-    n = fl[0].shape[0]
-    hs = [f.shape[1] for f in fl]
-    ws_ = [f.shape[2] for f in fl]
-    parts = torch.empty(sum(lib.of_ssim_partials(n, h, w) for h, w in zip(hs, ws_)),
+def _ssim_fwd(cfg, pyr, fl, want_grad):
+    """of_ssim_fwd_multi over every level (the SSIM data term, include/oflow.h).  The partials
+    sum to the weighted term (the coefficients are applied in the kernel); planes[l] is the
+    unscaled d SSIM_l / d flow, every element written, that of_ssim_bwd_multi scales into
+    d(flow).  The one entry takes the pixel weights of the window centres (NULL: 1) and the
+    convention."""
+    n, hs, ws = _dims(fl)
+    coefs = _ssim_coefs(n, hs, ws, cfg.ssw)
+    parts = torch.empty(sum(_lib.lib().of_ssim_partials(n, h, w) for h, w in zip(hs, ws)),
                         device=fl[0].device)
-    planes = [torch.empty_like(f) for f in fl] if want_grad else None
-    plp = _arr(C.c_void_p, [p.data_ptr() for p in planes]) if planes is not None else None
-    call("of_ssim_fwd_multi", _arr(C.c_void_p, [p.data_ptr() for p in pyr]),
-         _arr(C.c_void_p, [f.data_ptr() for f in fl]),
-         _opt_ptrs(wts) if wts is not None else None, n, _arr(C.c_int, hs), _arr(C.c_int, ws_),
-         ns, _arr(C.c_float, coefs), plp, _ptr(parts), wc, _stream())
-    return parts, planes
+    planes, plp = _planes(fl, want_grad)
+    call("of_ssim_fwd_multi", _ptrs(pyr), _ptrs(fl),
+         _opt_ptrs(cfg.wts) if cfg.wts is not None else None, *_levels(fl),
+         _arr(C.c_float, coefs), plp, _ptr(parts), cfg.wc, _stream())
+    return [(parts, 0, parts.numel(), 1.0)], planes or [], coefs
 
 
-def _ssim_bwd(planes, lv, coefs, dloss, accumulate):
-    """of_ssim_bwd_multi for the levels in ``lv``."""
-    m = len(lv)
-    n = planes[0].shape[0]
-    call("of_ssim_bwd_multi", _arr(C.c_void_p, [planes[k].data_ptr() for k, _, _ in lv]), n,
-         _arr(C.c_int, [planes[k].shape[1] for k, _, _ in lv]),
-         _arr(C.c_int, [planes[k].shape[2] for k, _, _ in lv]), m,
-         _arr(C.c_float, [coefs[k] for k, _, _ in lv]), _ptr(dloss),
-         _arr(C.c_void_p, [o.data_ptr() for _, o, _ in lv]),
-         _arr(C.c_int, [ld for _, _, ld in lv]), accumulate, _stream())
+def _ssim_bwd(cfg, coefs, planes, pyr, flows, lv, dloss, accumulate):
+    _planes_bwd("of_ssim_bwd_multi", planes, lv, coefs, dloss, accumulate)
+
+
+def _unit_planes_bwd(cfg, state, planes, pyr, flows, lv, dloss, accumulate):
+    """Planes that carry their coefficients (the supervised and the self-supervision term),
+    scaled by dloss into d(flow): of_census_bwd_multi with unit coefficients."""
+    _planes_bwd("of_census_bwd_multi", planes, lv, [1.0] * len(planes), dloss, accumulate)
 
 
 # ============================================================== supervised term =====
@@ -2369,40 +2367,30 @@ def _sup_level_weights(level_weights, ns):
     return lw
 
 
-def _sup_fwd(fl, gt, q, eps, coefs, want_grad):
-    """of_supervised_fwd_multi over every level (the supervised term, include/oflow.h):
-    (partials, per-level counts, planes).  Level l's slice of the partials sums to coefs[l] *
-    S_l (the coefficients are applied in the kernel); planes[l] is d(coefs[l] * S_l) / d flow,
-    every element written, that the pixelwise plane scaling (of_census_bwd_multi) turns into
-    d(flow), or None without want_grad.  ``gt``: (CUDA buffer, host descriptors) of the first
-    len(descriptors) images; the others have no ground truth."""
+def _sup_fwd(cfg, pyr, fl, want_grad):
+    """of_supervised_fwd_multi over every level (the supervised term, include/oflow.h).  Level
+    l's slice of the partials sums to coefs[l] * S_l (the coefficients, cfg.supw times the
+    level weights, are applied in the kernel); planes[l] is d(coefs[l] * S_l) / d flow, every
+    element written.  ``cfg.gt``: (CUDA buffer, host descriptors) of the first len(descriptors)
+    images; the others have no ground truth."""
     lib = _lib.lib()
-    ns = len(fl)
-    n = fl[0].shape[0]
-    raw, descs = gt
+    n, hs, ws = _dims(fl)
+    raw, descs = cfg.gt
     n_gt = len(descs)
     if not 1 <= n_gt <= n:
         raise ValueError("ground truth for %d images, flows for %d" % (n_gt, n))
-    hs = [f.shape[1] for f in fl]
-    ws_ = [f.shape[2] for f in fl]
+    coefs = [cfg.supw * v for v in _sup_level_weights(cfg.suplw, len(fl))]
     mh, mw = int(descs["h"].max(initial=1)), int(descs["w"].max(initial=1))
-    nparts = [lib.of_supervised_partials(n, h, w, mh, mw) for h, w in zip(hs, ws_)]
-    parts = torch.empty(sum(nparts), device=fl[0].device)
-    planes = [torch.empty_like(f) for f in fl] if want_grad else None
-    plp = _arr(C.c_void_p, [p.data_ptr() for p in planes]) if planes is not None else None
+    parts = torch.empty(sum(lib.of_supervised_partials(n, h, w, mh, mw) for h, w in zip(hs, ws)),
+                        device=fl[0].device)
+    planes, plp = _planes(fl, want_grad)
     wsb = lib.of_supervised_workspace_bytes(n, mh, mw)
     wsk, wsp, _ = _workspace(wsb, fl[0].device)
-    call("of_supervised_fwd_multi", _arr(C.c_void_p, [f.data_ptr() for f in fl]), n, n_gt,
-         _arr(C.c_int, hs), _arr(C.c_int, ws_), ns, _ptr(raw),
-         descs.ctypes.data_as(C.c_void_p), raw.numel(), mh, mw, q, eps, _arr(C.c_float, coefs),
-         wsp, wsb, plp, _ptr(parts), _stream())
-    return parts, nparts, planes
-
-
-def _sup_bwd(planes, lv, dloss, accumulate):
-    """The supervised planes scaled by dloss into d(flow): of_census_bwd_multi with unit
-    coefficients (the planes carry theirs)."""
-    _census_bwd(planes, lv, [1.0] * len(planes), dloss, accumulate)
+    n, chs, cws, ns = _levels(fl)
+    call("of_supervised_fwd_multi", _ptrs(fl), n, n_gt, chs, cws, ns, _ptr(raw),
+         descs.ctypes.data_as(C.c_void_p), raw.numel(), mh, mw, cfg.supq, cfg.supeps,
+         _arr(C.c_float, coefs), wsp, wsb, plp, _ptr(parts), _stream())
+    return [(parts, 0, parts.numel(), 1.0)], planes or [], None
 
 
 # ============================================================= self-supervision =====
@@ -2488,20 +2476,23 @@ def augment_gt(gt, records, img_hw):
     return out, descs
 
 
-def _self_fwd(f0, target, weight, q, eps, coef, want_grad):
-    """of_flow_distill_fwd on the finest flow (the self-supervision term, include/oflow.h):
-    (partials, plane).  The first target.shape[0] images are scored; the partials sum to coef *
-    S; the plane, shaped like ``f0``, is d(coef * S) / d f0, every element written (zeros for the
-    images past the target's), or None without want_grad."""
-    n_t, fh, fw = target.shape[:3]
+def _self_fwd(cfg, pyr, fl, want_grad):
+    """of_flow_distill_fwd on the finest flow (the self-supervision term, include/oflow.h)
+    against ``cfg.selftw`` = (target, weight).  The first target.shape[0] images are scored; the
+    partials sum to coef * S, coef = cfg.selfw over their cells of the flow's grid; the plane,
+    shaped like the flow, is d(coef * S) / d flow, every element written (zeros for the images
+    past the target's)."""
+    f0 = fl[0]
+    target, weight = cfg.selftw
+    n_t, fh, fw = target.shape[0], f0.shape[1], f0.shape[2]
     parts = torch.empty(_lib.lib().of_flow_distill_partials(n_t, fh, fw), device=f0.device)
     plane = torch.empty_like(f0) if want_grad else None
     if plane is not None and f0.shape[0] > n_t:
         rest = plane[n_t:]
         call("of_fill", _ptr(rest), 0.0, rest.numel(), _stream())
-    call("of_flow_distill_fwd", _ptr(f0), _ptr(target), _ptr(weight), n_t, fh, fw, q, eps, coef,
-         _ptr(plane), _ptr(parts), _stream())
-    return parts, plane
+    call("of_flow_distill_fwd", _ptr(f0), _ptr(target), _ptr(weight), n_t, fh, fw, cfg.selfq,
+         cfg.selfeps, cfg.selfw / (n_t * fh * fw), _ptr(plane), _ptr(parts), _stream())
+    return [(parts, 0, parts.numel(), 1.0)], [plane] if want_grad else [], None
 
 
 # ============================================================ the loss Function =====
@@ -2562,143 +2553,118 @@ class _LossCfg(NamedTuple):
     selftw: Optional[tuple] = None  # the finest flow
 
 
+class _Term(NamedTuple):
+    """One term of _Loss.  The table's order is the backward's order."""
+    name: str
+    on: Callable            # cfg -> its weight is not 0
+    groups: Callable        # level count -> the sum groups its forward returns
+    reads_pyramid: Callable     # cfg -> its forward reads the image pyramid
+    saves_pyramid: Callable     # cfg -> its backward needs the pyramid saved
+    flows: bool             # its backward needs the flows saved
+    fwd: Callable           # (cfg, pyr, fl, want_grad) -> (sum groups, tensors to save, state)
+    bwd: Callable           # (cfg, state, its saved tensors, pyr, flows, lv, dloss, accumulate)
+    finest: bool = False    # its backward writes level 0 alone
+
+
+def _yes(cfg):
+    return True
+
+
+def _no(cfg):
+    return False
+
+
+def _edges(cfg):
+    return cfg.edge_alpha != 0
+
+
+_TERMS = (
+    _Term("photometric", lambda cfg: cfg.pw != 0, lambda ns: ns, _yes, _yes, True,
+          _photo_fwd, _photo_bwd),
+    _Term("census", lambda cfg: cfg.cw != 0, lambda ns: 1, _yes, _no, False,
+          _census_fwd, _census_bwd),
+    _Term("SSIM", lambda cfg: cfg.ssw != 0, lambda ns: 1, _yes, _no, False,
+          _ssim_fwd, _ssim_bwd),
+    _Term("supervised", lambda cfg: cfg.supw != 0, lambda ns: 1, _no, _no, False,
+          _sup_fwd, _unit_planes_bwd),
+    _Term("self-supervision", lambda cfg: cfg.selfw != 0, lambda ns: 1, _no, _no, False,
+          _self_fwd, _unit_planes_bwd, finest=True),
+    _Term("smoothness", lambda cfg: cfg.sw != 0, lambda ns: 1, _edges, _edges, True,
+          _smooth_fwd, _smooth_bwd),
+)
+
+
 class _Loss(torch.autograd.Function):
-    """pw * photometric + cw * census + ssw * SSIM + supw * supervised + selfw * self-supervision
-    + sw * smoothness, each
-    the mean over the levels of that level's mean (the supervised term: its own level weights,
-    against the ground truth ``cfg.gt``; the self-supervision term: the finest flow only, against
-    ``cfg.selftw``, the mean over all cells of its first images), on one image pyramid; the images
-    are constants.  A term whose
-    weight is 0 launches nothing, and the pyramid is only built when a term reads it (a data
-    term, or the smoothness term with edge_alpha != 0).  The smoothness term is never weighted
-    by ``wts``.
+    """The sum of the terms of _TERMS whose weight in ``cfg`` is not 0, each the mean over the
+    levels of that level's mean (the supervised term: its own level weights, against the ground
+    truth ``cfg.gt``; the self-supervision term: the finest flow only, against ``cfg.selftw``,
+    the mean over all cells of its first images), on one image pyramid; the images are
+    constants.  A term whose weight is 0 launches nothing, and the pyramid is only built when a
+    term reads it (a data term, or the smoothness term with edge_alpha != 0).  The smoothness
+    term is never weighted by ``wts``.
 
     One Function for all terms because of the FlowGrad protocol: the loss writes a flow's
     gradient buffer once and upscale_flow's backward adds to it afterwards, so two Functions
-    returning gradients for the same flow would break it.  In the backward the terms run
-    photometric, census, SSIM, supervised, self-supervision (level 0 only), smoothness; the first
-    one present overwrites each level's
-    d(flow) output and the later ones add into it (``accumulate = 1``)."""
+    returning gradients for the same flow would break it.  In the backward the terms run in the
+    table's order; the first one present overwrites each level's d(flow) output and the later
+    ones add into it (``accumulate = 1``)."""
 
     @staticmethod
     def forward(ctx, batch_imgs, cfg, *flows):
-        pw, cw, sw, ssw = cfg.pw, cfg.cw, cfg.sw, cfg.ssw
         _check_dev(batch_imgs, *flows)
         ns = len(flows)
         assert 1 <= ns <= 8, "the loss kernels take 8 levels"
-        supw, selfw = cfg.supw, cfg.selfw
-        ngroups = ((ns if pw else 0) + (cw != 0) + (ssw != 0) + (sw != 0) + (supw != 0) +
-                   (selfw != 0))
+        terms = [t for t in _TERMS if t.on(cfg)]
+        ngroups = sum(t.groups(ns) for t in terms)
         if ngroups > 8:
-            raise ValueError("of_sum_partials takes 8 groups (one per photometric level, census, "
-                             "SSIM, supervised, self-supervision, smoothness): this loss needs %d"
-                             % ngroups)
-        # the self-supervision term writes level 0 alone: it may open the backward only when
-        # there is no other level
-        assert selfw == 0 or ns == 1 or pw != 0 or cw != 0 or ssw != 0 or supw != 0
+            raise ValueError("of_sum_partials takes 8 groups (%s): this loss needs %d"
+                             % (", ".join("%d for %s" % (t.groups(ns), t.name) for t in terms),
+                                ngroups))
+        # a term that writes level 0 alone may open the backward only when there is no other
+        # level
+        assert ns == 1 or not any(t.finest for t in terms[:1])
         fl = [f.contiguous() for f in flows]
-        n = fl[0].shape[0]
-        hs = [f.shape[1] for f in fl]
-        ws_ = [f.shape[2] for f in fl]
         want_grad = any(ctx.needs_input_grad[2:])
         pyr = []
-        if pw != 0 or cw != 0 or ssw != 0 or cfg.edge_alpha != 0:
+        if any(t.reads_pyramid(cfg) for t in terms):
             pyr = _pyramid6(batch_imgs.contiguous(), fl)
-        # The sum's groups are raw (pointer, count, coefficient): ``keep`` holds the partial
+        # The sum's groups are raw (pointer, count, coefficient): ``groups`` holds the partial
         # arrays until the sum is enqueued.  A dropped one's memory could be handed to the next
         # term's partials or to ``loss`` and be overwritten ahead of the sum on this stream.
-        groups, keep = [], []
-        coefs = ccoefs = scoefs = cv = ch = planes = splanes = None    # of the terms that are off
-        supplanes = selfplane = None
-        if pw != 0:
-            coefs = [pw / (ns * n * h * w * 3) for h, w in zip(hs, ws_)]
-            parts, nparts = _photo_fwd(pyr, fl, cfg.wts, cfg.wc)
-            off = 0
-            for k in range(ns):
-                groups.append((parts.data_ptr() + 4 * off, nparts[k], coefs[k]))
-                off += nparts[k]
-            keep.append(parts)
-        # the census and smoothness partials carry their coefficients: one group each
-        if cw != 0:
-            ccoefs = _census_coefs(n, hs, ws_, cw)
-            cparts, planes = _census_fwd(pyr, fl, cfg.radius, ccoefs, want_grad, cfg.wc, cfg.wts)
-            groups.append((cparts.data_ptr(), cparts.numel(), 1.0))
-            keep.append(cparts)
-        if ssw != 0:
-            scoefs = _ssim_coefs(n, hs, ws_, ssw)
-            ssparts, splanes = _ssim_fwd(pyr, fl, scoefs, want_grad, cfg.wc, cfg.wts)
-            groups.append((ssparts.data_ptr(), ssparts.numel(), 1.0))
-            keep.append(ssparts)
-        if supw != 0:
-            lw = _sup_level_weights(cfg.suplw, ns)
-            supparts, _, supplanes = _sup_fwd(fl, cfg.gt, cfg.supq, cfg.supeps,
-                                              [supw * v for v in lw], want_grad)
-            groups.append((supparts.data_ptr(), supparts.numel(), 1.0))
-            keep.append(supparts)
-        if selfw != 0:
-            tgt, wt = cfg.selftw
-            selfparts, selfplane = _self_fwd(fl[0], tgt, wt, cfg.selfq, cfg.selfeps,
-                                             selfw / (tgt.shape[0] * hs[0] * ws_[0]), want_grad)
-            groups.append((selfparts.data_ptr(), selfparts.numel(), 1.0))
-            keep.append(selfparts)
-        if sw != 0:
-            cv, ch = _smooth_coefs(n, hs, ws_, sw, cfg.order)
-            sparts = _smooth_fwd(pyr, fl, cfg.edge_alpha, cfg.eps, cv, ch, cfg.order)
-            groups.append((sparts.data_ptr(), sparts.numel(), 1.0))
-            keep.append(sparts)
+        groups, own, ctx.states = [], [], []
+        for t in terms:
+            g, save, state = t.fwd(cfg, pyr, fl, want_grad)
+            groups += g
+            own.append(save)
+            ctx.states.append(state)
         loss = torch.empty((), device=fl[0].device)
-        call("of_sum_partials", _arr(C.c_void_p, [g[0] for g in groups]),
-             _arr(C.c_int, [g[1] for g in groups]), _arr(C.c_float, [g[2] for g in groups]),
+        call("of_sum_partials", _arr(C.c_void_p, [g[0].data_ptr() + 4 * g[1] for g in groups]),
+             _arr(C.c_int, [g[2] for g in groups]), _arr(C.c_float, [g[3] for g in groups]),
              len(groups), _ptr(loss), _stream())
         # Saved: only what a backward of a term that is on reads.  The pyramid: photometric,
         # and smoothness with edge_alpha != 0; the flows: photometric and smoothness; census,
         # SSIM, the supervised and the self-supervision term keep just their planes.
-        keep_pyr = pyr if pw != 0 or (sw != 0 and cfg.edge_alpha != 0) else []
-        keep_fl = fl if pw != 0 or sw != 0 else []
-        ctx.save_for_backward(*keep_pyr, *keep_fl, *(planes or []), *(splanes or []),
-                              *(supplanes or []), *([selfplane] if selfplane is not None else []))
-        ctx.split = (len(keep_pyr), len(keep_pyr) + len(keep_fl),
-                     len(keep_pyr) + len(keep_fl) + len(planes or []),
-                     len(keep_pyr) + len(keep_fl) + len(planes or []) + len(splanes or []),
-                     len(keep_pyr) + len(keep_fl) + len(planes or []) + len(splanes or []) +
-                     len(supplanes or []))
-        ctx.wts = cfg.wts if pw != 0 else None      # the photometric backward reads them again
+        keep_pyr = pyr if any(t.saves_pyramid(cfg) for t in terms) else []
+        keep_fl = fl if any(t.flows for t in terms) else []
+        ctx.save_for_backward(*keep_pyr, *keep_fl, *[s for o in own for s in o])
+        ctx.counts = [len(keep_pyr), len(keep_fl)] + [len(o) for o in own]
         ctx.cfg = cfg._replace(wts=None, gt=None, selftw=None)
-        ctx.coefs = (coefs, ccoefs, cv, ch, scoefs)
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
         cfg = ctx.cfg
-        coefs, ccoefs, cv, ch, scoefs = ctx.coefs
-        saved = ctx.saved_tensors
-        a, b, c, d, e = ctx.split
-        pyr, flows, planes, splanes = saved[:a], saved[a:b], saved[b:c], saved[c:d]
-        supplanes, selfplanes = saved[d:e], saved[e:]
+        saved = iter(ctx.saved_tensors)
+        pyr, flows, *own = [[next(saved) for _ in range(c)] for c in ctx.counts]
         dloss = dloss.contiguous()
-        grads, lv = _grad_targets(cfg.fgs, flows or planes or splanes or supplanes or selfplanes,
+        grads, lv = _grad_targets(cfg.fgs, flows or next((o for o in own if o), []),
                                   ctx.needs_input_grad[2:])
-        if lv:
-            written = 0                # the first term present writes, the others add
-            if cfg.pw != 0:
-                _photo_bwd(pyr, flows, ctx.wts, lv, coefs, dloss, cfg.wc)
+        written = 0                # the first term present writes, the others add
+        for t, state, mine in zip([t for t in _TERMS if t.on(cfg)], ctx.states, own):
+            tl = [x for x in lv if x[0] == 0] if t.finest else lv
+            if tl:
+                t.bwd(cfg, state, mine, pyr, flows, tl, dloss, written)
                 written = 1
-            if cfg.cw != 0:
-                _census_bwd(planes, lv, ccoefs, dloss, written)
-                written = 1
-            if cfg.ssw != 0:
-                _ssim_bwd(splanes, lv, scoefs, dloss, written)
-                written = 1
-            if cfg.supw != 0:
-                _sup_bwd(supplanes, lv, dloss, written)
-                written = 1
-            lv0 = [t for t in lv if t[0] == 0]
-            if cfg.selfw != 0 and lv0:
-                _sup_bwd(selfplanes, lv0, dloss, written)
-                written = 1
-            if cfg.sw != 0:
-                _smooth_bwd(pyr, flows, lv, cfg.edge_alpha, cfg.eps, cv, ch, dloss, written,
-                            cfg.order)
         return (None, None, *grads)
 
 

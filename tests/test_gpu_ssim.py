@@ -402,14 +402,16 @@ def test_loss_layer_with_ssim_and_occlusion(mode):
 
 # --------------------------------------------------------------------------- 6. off switch ----
 def _rows():
-    from test_gpu_loss_paths import ROWS
-    return list(ROWS)
+    """The dispatch rows of test_gpu_loss_paths.py that leave the SSIM term off."""
+    from test_gpu_loss_paths import ROWS, SSF
+    return [row for row, (_, fwd, _) in ROWS.items() if SSF not in fwd]
 
 
 @pytest.mark.parametrize("row", _rows())
 def test_off_switch(monkeypatch, row):
     """With ssim_weight = 0 no of_ssim* entry is called, forward or backward, by any dispatch
-    row of test_gpu_loss_paths.py; with it on, the forward and the backward entry are."""
+    row of test_gpu_loss_paths.py that has no SSIM term; with it on, the forward and the
+    backward entry are."""
     from optical_flow_amd import ops
     from test_gpu_loss_paths import ROWS, _inputs
     batch, flows = _inputs()
